@@ -11,11 +11,18 @@ Inputs are generated on the device (seeded by global slice index) and are reside
 before the timed region.  One unit of work = one stored non-zero of one slice ("edge-slice").
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full # every leg below as well
     python bench.py --gpus 8 --steps 10 --warmup 3        # starts its own 8 ranks (see launch())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 10 --warmup 3
 
-Rank 0 prints ONE JSON line (driver contract), the last line of the job's stdout, with
+A plain run is lean: it sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs DIR is
+given, and prints the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, the in-run per-kernel
+times and the roofline on them, the traffic of the committed PMC record).  Everything that takes checks or runs of its
+own — the verify leg, the measured traffic, the hbm-only and side legs, the exchange comparison, the epochs and the CPU
+baseline — runs with --full only (FULL_ONLY).
+
+Rank 0 prints ONE JSON line (driver contract), the last line of the job's stdout, with (--full: all of them)
   roofline      dominant kernel = the fused SpMM+GEMM kernel (its forward and backward launches: the average rocprofv3's
                 per-kernel row reports; each direction beside it), HIP events on the launch stream; `traffic` measured in
                 the run (two PMC child runs); `roofline.legs` = the side legs' figures:
@@ -131,7 +138,17 @@ def parse(argv=None):
                         "the GPU, so that the deadline path can be exercised on a CPU-only machine")
     p.add_argument("--deadline", type=int, default=900,
                    help="hard limit: after this many seconds every rank dumps its stacks and exits non-zero (0 disables)")
+    p.add_argument("--full", action="store_true",
+                   help="run everything beyond the headline as well: the verify leg, the measured traffic, the hbm-only and side "
+                        "legs, the exchange comparison, the epochs and the CPU baseline (a plain run skips them: FULL_ONLY)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed (Y, dX, dW of rank 0's shard) as DIR/<name>.npy, "
+                        "float32; Y and dX as a fixed, seeded sample of their rows (dump_outputs)")
     return p.parse_args(argv)
+
+
+# what a plain run leaves out (the --no-* switches a run without --full gets)
+FULL_ONLY = ("no_verify", "no_measure_traffic", "no_hbm_only", "no_legs", "no_compare_exchange", "no_epochs", "no_cpu_baseline")
 
 
 def stage(msg):
@@ -519,9 +536,9 @@ def build_problem(args, dev, rank, world, exchange, N, kernels_ok=True):
                 x_slice=x_slice, dy_slice=dy_slice, a_slice=a_slice)
 
 
-def run_layer(args, dist, dev, rank, world, exchange, N, steps, warmup, want_timer=True, verify=False):
-    """Build this rank's shard of the S4 layer at N nodes and time `steps` fwd+bwd steps.
-    Returns a dict; every device tensor dies with this frame."""
+def run_layer(args, dist, dev, rank, world, exchange, N, steps, warmup, want_timer=True, verify=False, dump_dir=None):
+    """Build this rank's shard of the S4 layer at N nodes and time `steps` fwd+bwd steps; rank 0 writes the last step's
+    outputs to `dump_dir` if given.  Returns a dict; every device tensor dies with this frame."""
     import torch
     from tmgcn_amd import ops
 
@@ -591,6 +608,9 @@ def run_layer(args, dist, dev, rank, world, exchange, N, steps, warmup, want_tim
         total_nnz = A.nnz
     stage(f"layer[{exchange}, N={N}]: {elapsed / steps * 1e3:.1f} ms/step")
     peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, {"Y": last["Y"], "dX": X.grad, "dW": W.grad})
+        stage(f"layer[{exchange}, N={N}]: last step's outputs written to {dump_dir}")
     ver = None
     if verify:
         # the checker: the results of the LAST TIMED step against the CPU oracle, from regenerated inputs
@@ -615,6 +635,27 @@ def run_layer(args, dist, dev, rank, world, exchange, N, steps, warmup, want_tim
             "gather_chunks": len(layer.gather_chunks(F)) if (layer.collective and exchange == "allgather"
                                                                and layer.gather_chunk_nodes != 0) else None,
             "peak_gb": peak_gb, "verify": ver, "phases": phases_rec}
+
+
+DUMP_BYTES = 20 << 20  # per array: Y and dX of the S4 shard (16 GB each) are sampled down to this, the three stay below 64 MB
+
+
+def dump_outputs(dump_dir, arrays):
+    """`arrays` (name -> device tensor [..., F]) as dump_dir/<name>.npy, float32.  An array larger than DUMP_BYTES is
+    written as a sample of its rows (rows = every index but the last): a fixed number of distinct rows drawn by a
+    generator seeded with 0, in ascending order, gathered in place — so two runs of the same shape write the same rows."""
+    import numpy as np
+    import torch
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        lead, F = tuple(t.shape[:-1]), t.shape[-1]
+        n = int(np.prod(lead))
+        k = max(1, DUMP_BYTES // (4 * F))
+        if n > k:
+            idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+            t = t[tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(idx, lead))]
+        np.save(os.path.join(dump_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def _child_env():
@@ -642,7 +683,7 @@ def run_child(flags, what, timeout=420):
     """One child run of this script (an ordinary child process of a parent that has released its device memory; a profiler
     around the parent then sees the headline's launches only).  Returns (parsed JSON line or None, exit code, error text)."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__)] + flags + CHILD_OFF
+    cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--full"] + CHILD_OFF
     stage(f"{what}: child run {' '.join(flags)}")
     try:
         r = subprocess.run(cmd, cwd=ROOT, env=_child_env(), capture_output=True, text=True, timeout=timeout)
@@ -849,7 +890,16 @@ def traffic_record(N, F, Tl):
     return None, None
 
 
+def plain_or_full(args):
+    """A run without --full is the headline alone: it gets every FULL_ONLY switch."""
+    if not args.full:
+        for k in FULL_ONLY:
+            setattr(args, k, True)
+    return args
+
+
 def worker(args):
+    plain_or_full(args)
     arm_deadlines(args)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -935,7 +985,8 @@ def worker(args):
     if not ok:
         raise SystemExit(f"bench: the '{args.exchange}' plan needs {need / 1e9:.0f} GB per rank but only {free_b / 1e9:.0f} GB "
                          f"are free (rank {rank}); nothing was allocated")
-    res = run_layer(args, dist, dev, rank, world, args.exchange, N, args.steps, args.warmup, verify=not args.no_verify)
+    res = run_layer(args, dist, dev, rank, world, args.exchange, N, args.steps, args.warmup, verify=not args.no_verify,
+                    dump_dir=args.dump_outputs)
     free_device_memory()
     hbm_only = None
     if world == 1 and not collective and not args.no_hbm_only and Tl >= 4:

@@ -141,6 +141,51 @@ def test_side_leg_record_is_composed_from_the_child_line(monkeypatch):
     assert seen["flags"][seen["flags"].index("--slices-per-gpu") + 1] == "128" and seen["flags"][seen["flags"].index("--nodes") + 1] == "250000"
 
 
+def test_plain_run_is_the_headline_alone_and_full_keeps_every_leg(monkeypatch):
+    """A run without --full gets every FULL_ONLY switch (no verify, measured traffic, hbm-only or side legs, exchange
+    comparison, epochs or CPU baseline); --full leaves the switches as given, and the side legs' child runs ask for
+    --full so that they still verify themselves."""
+    import subprocess
+    import bench
+    plain = bench.plain_or_full(bench.parse(["--steps", "7"]))
+    assert plain.steps == 7 and all(getattr(plain, k) is True for k in bench.FULL_ONLY)
+    full = bench.plain_or_full(bench.parse(["--full", "--no-epochs"]))
+    assert full.no_epochs and not any(getattr(full, k) for k in bench.FULL_ONLY if k != "no_epochs")
+    seen = {}
+
+    class Done:
+        returncode, stdout, stderr = 0, '{"ok": 1}\n', ""
+
+    def fake_run(cmd, **kw):
+        seen["cmd"] = cmd
+        return Done()
+
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    line, rc, err = bench.run_child(bench.workload_flags(full), "leg")
+    assert line == {"ok": 1} and rc == 0 and err is None
+    assert "--full" in seen["cmd"] and "--no-verify" not in seen["cmd"]
+
+
+def test_dump_outputs_writes_a_fixed_sample_below_the_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy per array; an array above DUMP_BYTES becomes the same seeded rows on every call,
+    small ones are written whole."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    Y = torch.randn(3, 500, 32, dtype=torch.float64)
+    W = torch.randn(32, 32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"Y": Y, "dW": W})
+    y, w = np.load(tmp_path / "a" / "Y.npy"), np.load(tmp_path / "a" / "dW.npy")
+    assert y.dtype == np.float32 and y.shape == (512, 32) and y.nbytes <= 64 << 10
+    assert np.array_equal(y, np.load(tmp_path / "b" / "Y.npy"))
+    rows = Y.reshape(-1, 32).float().numpy()
+    assert all(any(np.array_equal(r, q) for q in rows) for r in y[:8])                  # rows of Y, not a reduction of them
+    assert len({r.tobytes() for r in y}) == 512                                           # distinct rows
+    assert np.array_equal(w, W.numpy())
+
+
 def test_timeline_gaps_tool_unions_overlapping_kernels(tmp_path):
     """tools/timeline_gaps.py on a synthetic kernel trace: two steps, kernels of two streams overlapping,
     one idle gap — busy time is the UNION of the intervals, the gap is attributed to its neighbours."""

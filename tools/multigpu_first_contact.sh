@@ -18,7 +18,7 @@ echo "pytest test_gpu_multi rc=$?" | tee -a "$OUT/status.log"; tail -3 "$OUT/pyt
 #    exchange_compare.full_n — DESIGN.md §6 has the predicted table; tools/predict_scaling.py reproduces it)
 for g in 1 2 4 8; do
   [ "$g" -le "$MAX" ] || continue
-  timeout 1800 python3 bench.py --gpus $g --steps 20 --warmup 5 --no-epochs --no-cpu-baseline > "$OUT/scale_g$g.json" 2> "$OUT/scale_g$g.err"
+  timeout 1800 python3 bench.py --gpus $g --steps 20 --warmup 5 --full --no-epochs --no-cpu-baseline > "$OUT/scale_g$g.json" 2> "$OUT/scale_g$g.err"
   echo "bench --gpus $g rc=$? $(grep -h 'headline' "$OUT/scale_g$g.err" | tail -1 | sed 's/.*headline: //')" | tee -a "$OUT/status.log"
 done
 

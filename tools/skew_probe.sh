@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for g in $GRAPHS; do
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$g" -- python3 "$ROOT/bench.py" --graph "$g" --steps 5 --warmup 2 \
-    --no-epochs --no-cpu-baseline --no-hbm-only --no-measure-traffic > "$OUT/bench_$g.json" 2> "$OUT/bench_$g.log"
+    --full --no-epochs --no-cpu-baseline --no-hbm-only --no-measure-traffic > "$OUT/bench_$g.json" 2> "$OUT/bench_$g.log"
   echo "$g rc=$?"
   tail -1 "$OUT/bench_$g.json" | python3 -c "
 import json,sys
