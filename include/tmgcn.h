@@ -44,7 +44,8 @@ typedef enum {
 /* activation ids for the fused P3 epilogue / P5 pointwise (ehf:284-289, 455-460) */
 enum { TMGCN_ACT_NONE = 0, TMGCN_ACT_RELU = 1, TMGCN_ACT_LEAKY = 2, TMGCN_ACT_SELU = 3 };
 
-/* ABI version 5 = version 4 + tmgcn_pool_stats + the row_blocks partition argument of tmgcn_layer12_fwd/bwd_f32, the backward's AX / dW2 pair and tmgcn_layer12_bwd_forms_dw2 + tmgcn_head_loss_combine_f32 / tmgcn_head_loss_lanes (split rows of the one-pass head + loss plan) + the giant-row
+/* Additions to ABI version 5 (backward compatible, the version stays 5): the WD-GCN entry points tmgcn_wdgcn_* (below).
+ * ABI version 5 = version 4 + tmgcn_pool_stats + the row_blocks partition argument of tmgcn_layer12_fwd/bwd_f32, the backward's AX / dW2 pair and tmgcn_layer12_bwd_forms_dw2 + tmgcn_head_loss_combine_f32 / tmgcn_head_loss_lanes (split rows of the one-pass head + loss plan) + the giant-row
  *   plan entry points tmgcn_spmm_csr_batched_f32_plan / tmgcn_spmm_gemm_f32_plan / tmgcn_spmm_giant_workspace_bytes; the launchers' scratch words (tile counters, hand-off blocks) are kept apart
  *   per stream (eager launches) and per recorded launch (hipGraph capture), and a launcher that cannot keep two launches
  *   apart returns TMGCN_ERR_INVALID with the reason instead of re-using a word that may be in flight (csrc/pools.hip).
@@ -478,6 +479,31 @@ int tmgcn_adj_keys_to_csr(const uint64_t* key, int64_t n, int64_t N, int64_t TN,
 /* keys (slice, col, row) of every entry of a batched CSR: sort them to get the per-slice transpose */
 int tmgcn_adj_transpose_keys(const int64_t* rowptr, const int32_t* col, int64_t TN, int64_t N,
                              uint64_t* okey, void* stream);
+
+/* ---- WD-GCN: GCN input map + LSTM recurrence over the slices (additions to ABI 5) -------------
+ * TensorGCN-master/wd_gcn_functions.py ("wgf"), the WD_GCN / WD_GCN_reg models:
+ *   Y = relu(AX·W)                                                                  wgf:70
+ *   h = h0, c = c0 (every node); for t = 0..T_run-1:                                wgf:86-98
+ *     f = σ(Y_t Wf + h Uf + bf)  j = σ(Y_t Wj + h Uj + bj)  o = σ(Y_t Wo + h Uo + bo)
+ *     ct = σ(Y_t Wc + h Uc + bc)  c = j·ct + f·c  h = o·tanh(c)  Z_t = h
+ * AX [>= T_run][N][F0] (only the first T_run slices are read), Z and C [T_run][N][H].  The recurrence is causal:
+ * a caller whose consumer reads slices < T_run only may stop there, the slices it gets are the same bits.
+ * P: the 13 parameters packed in the reference's order (wgf:36-51), tmgcn_wdgcn_param_count(F0, H) floats:
+ *   W [F0][H] | Wf Wj Wc Wo [H][H] | Uf Uj Uc Uo [H][H] | bf bj bc bo [H]
+ * h0, c0 [H]: the model's h_init / c_init.  Supported when tmgcn_wdgcn_supported(F0, H): 1 <= F0 <= 8, 1 <= H <= 8.
+ * Forward: C = NULL stores no cell state (no gradient will be asked for); otherwise C receives c_t of every step.
+ * Backward (BPTT, autograd of the statements above with respect to the 13 parameters): dZ [T_run][N][H] in, dP
+ * (packed like P) out; the gates are recomputed from Z and C of the forward.  No atomics: fixed summation order, the
+ * same bits on every run.  workspace >= tmgcn_wdgcn_bwd_workspace_bytes(N, F0, H) (-1: unsupported widths).
+ * N == 0 or T_run == 0: the forward is a no-op, the backward writes dP = 0. */
+int tmgcn_wdgcn_supported(int32_t F0, int32_t H);
+int64_t tmgcn_wdgcn_param_count(int32_t F0, int32_t H);
+int tmgcn_wdgcn_fwd_f32(const float* AX, const float* P, const float* h0, const float* c0, float* Z, float* C,
+                        int64_t N, int32_t T_run, int32_t F0, int32_t H, void* stream);
+int64_t tmgcn_wdgcn_bwd_workspace_bytes(int64_t N, int32_t F0, int32_t H);
+int tmgcn_wdgcn_bwd_f32(const float* AX, const float* P, const float* h0, const float* c0, const float* Z,
+                        const float* C, const float* dZ, float* dP, int64_t N, int32_t T_run, int32_t F0,
+                        int32_t H, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

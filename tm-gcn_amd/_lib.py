@@ -86,6 +86,11 @@ SIGNATURES = {
     "tmgcn_adj_transpose_keys": (C.c_int, [_p, _p, _i64, _i64, _p, _p]),
     "tmgcn_act_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _p]),
     "tmgcn_act_bwd_f32": (C.c_int, [_p, _p, _p, _i64, _i32, _p]),
+    "tmgcn_wdgcn_supported": (C.c_int, [_i32, _i32]),
+    "tmgcn_wdgcn_param_count": (_i64, [_i32, _i32]),
+    "tmgcn_wdgcn_fwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p]),
+    "tmgcn_wdgcn_bwd_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "tmgcn_wdgcn_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _i64, _p]),
 }
 
 _lib = None

@@ -13,9 +13,10 @@
 //     tmgcn::edge_head_fwd/bwd   tmgcn_edge_head_*_f32             ehf:228-232, 351-355, 491-495
 //     tmgcn::act_fwd/bwd         tmgcn_act_*_f32                   ehf:284-289
 //     tmgcn::wce_fwd/bwd         tmgcn_wce_*_f32                   experiment_reddit_our_link_prediction.py:69, 79
+//     tmgcn::wdgcn_fwd/bwd       tmgcn_wdgcn_*_f32                 wd_gcn_functions.py:70, 86-98 (WD-GCN)
 //   differentiable ops (registered under the Autograd key)
 //     tmgcn::m_transform, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm,
-//     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce
+//     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce, tmgcn::wdgcn_lstm
 //
 // No kernels live here: every launch goes through the C-ABI shared library (libtmgcn_hip.so),
 // on torch's current HIP stream.  Errors surface as RuntimeError (TORCH_CHECK), the reference's
@@ -619,6 +620,61 @@ std::vector<Tensor> widen_params_ad(at::TensorList params) { return WidenFn::app
 
 bool spmm_gemm_supported(int64_t K, int64_t Nf) { return tmgcn_spmm_gemm_supported((int32_t)K, (int32_t)Nf) != 0; }
 bool layer12_supported(int64_t K0, int64_t F, int64_t Nf) { return tmgcn_layer12_supported((int32_t)K0, (int32_t)F, (int32_t)Nf) != 0; }
+// ---- WD-GCN (wd_gcn_functions.py:66-98): relu(AX·W) + the LSTM recurrence, and its BPTT ----------------------------
+bool wdgcn_supported(int64_t F0, int64_t H) { return tmgcn_wdgcn_supported((int32_t)F0, (int32_t)H) != 0; }
+
+static void wdgcn_check(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
+  want(AX, "wdgcn AX");
+  want(P, "wdgcn P");
+  want(h0, "wdgcn h0");
+  want(c0, "wdgcn c0");
+  TORCH_CHECK(AX.dim() == 3, "wdgcn: AX must be [T, N, F0], got ", AX.sizes());
+  const int64_t F0 = AX.size(2);
+  TORCH_CHECK(tmgcn_wdgcn_supported((int32_t)F0, (int32_t)H), "wdgcn: F0=", F0, ", H=", H,
+              " outside the kernel's widths (1..8 each)");
+  TORCH_CHECK(T_run >= 0 && T_run <= AX.size(0), "wdgcn: T_run=", T_run, " outside 0..", AX.size(0));
+  TORCH_CHECK(P.numel() == tmgcn_wdgcn_param_count((int32_t)F0, (int32_t)H), "wdgcn: P holds ", P.numel(),
+              " floats, the packed parameters of F0=", F0, ", H=", H, " are ", tmgcn_wdgcn_param_count((int32_t)F0, (int32_t)H));
+  TORCH_CHECK(h0.numel() == H && c0.numel() == H, "wdgcn: h0 / c0 must hold H=", H, " values");
+}
+
+// Z [T_run, N, H] and, with need_c, the cell state of every step (what the backward recomputes the gates from)
+std::tuple<Tensor, Tensor> wdgcn_fwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H,
+                                     int64_t T_run, bool need_c) {
+  wdgcn_check(AX, P, h0, c0, H, T_run);
+  c10::DeviceGuard g(AX.device());
+  const int64_t N = AX.size(1);
+  Tensor Z = at::empty({T_run, N, H}, AX.options());
+  Tensor C = need_c ? at::empty({T_run, N, H}, AX.options()) : none_like(AX);
+  ok(tmgcn_wdgcn_fwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
+                         (float*)ptr(Z), need_c ? (float*)ptr(C) : nullptr, N, (int32_t)T_run, (int32_t)AX.size(2),
+                         (int32_t)H, stream_of(AX)),
+     "tmgcn_wdgcn_fwd_f32");
+  return {Z, C};
+}
+
+// dP (packed like P) from dZ [T_run, N, H]
+Tensor wdgcn_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, const Tensor& Z, const Tensor& C,
+                 const Tensor& dZ) {
+  const int64_t H = Z.dim() == 3 ? Z.size(2) : -1, T_run = Z.dim() == 3 ? Z.size(0) : -1;
+  wdgcn_check(AX, P, h0, c0, H, T_run);
+  want(Z, "wdgcn Z");
+  want(C, "wdgcn C");
+  want(dZ, "wdgcn dZ");
+  const int64_t N = AX.size(1), F0 = AX.size(2);
+  TORCH_CHECK(Z.size(1) == N && C.sizes() == Z.sizes() && dZ.sizes() == Z.sizes(), "wdgcn_bwd: Z ", Z.sizes(), ", C ",
+              C.sizes(), ", dZ ", dZ.sizes(), " must all be [T_run, N=", N, ", H]");
+  c10::DeviceGuard g(AX.device());
+  Tensor dP = at::empty({P.numel()}, P.options());
+  const int64_t need = tmgcn_wdgcn_bwd_workspace_bytes(N, (int32_t)F0, (int32_t)H);
+  Tensor ws = at::empty({need > 0 ? need : 1}, AX.options().dtype(at::kByte));
+  ok(tmgcn_wdgcn_bwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
+                         (const float*)ptr(Z), (const float*)ptr(C), (const float*)ptr(dZ), (float*)ptr(dP), N,
+                         (int32_t)T_run, (int32_t)F0, (int32_t)H, ptr(ws), ws.numel(), stream_of(AX)),
+     "tmgcn_wdgcn_bwd_f32");
+  return dP.view(P.sizes());
+}
+
 bool edge_head_supported(int64_t F, int64_t C) { return tmgcn_edge_head_supported((int32_t)F, (int32_t)C) != 0; }
 bool head_loss_supported(int64_t F, int64_t C, int64_t K) { return tmgcn_head_loss_supported((int32_t)F, (int32_t)C, (int32_t)K) != 0; }
 int64_t abi_version() { return tmgcn_abi_version(); }
@@ -967,6 +1023,25 @@ struct Layer12Fn : public torch::autograd::Function<Layer12Fn> {
   }
 };
 
+// the WD-GCN embedding Z = LSTM(relu(AX·W)) over the first T_run slices; the gradient is taken with respect to the
+// packed parameters P only (AX, h_init, c_init are constants of the reference's model: wgf:52-53, 80-84)
+struct WdgcnLstmFn : public torch::autograd::Function<WdgcnLstmFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0,
+                        int64_t H, int64_t T_run, bool need) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    auto [Z, C] = wdgcn_fwd(AX, P, h0, c0, H, T_run, need);
+    if (need) ctx->save_for_backward({AX, P, h0, c0, Z, C});
+    return Z;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    auto sv = ctx->get_saved_variables();
+    Tensor dZ = grads[0].defined() ? grads[0].contiguous() : at::zeros_like(sv[4]);
+    return {Tensor(), wdgcn_bwd(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], dZ), Tensor(), Tensor(), Tensor(), Tensor(),
+            Tensor()};
+  }
+};
+
 struct ActivationFn : public torch::autograd::Function<ActivationFn> {
   static Tensor forward(AutogradContext* ctx, const Tensor& x, int64_t act) {
     at::AutoDispatchBelowADInplaceOrView guard;
@@ -1041,6 +1116,12 @@ Tensor layer12_ad(const Tensor& H, const Tensor& W1, const Tensor& W2, const Ten
                           grad && W1.requires_grad(), grad && W2.requires_grad());
 }
 Tensor activation_ad(const Tensor& x, int64_t act) { return ActivationFn::apply(x, act); }
+Tensor wdgcn_lstm_ad(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
+  const bool grad = at::GradMode::is_enabled();
+  TORCH_CHECK(!(grad && (AX.requires_grad() || h0.requires_grad() || c0.requires_grad())),
+              "wdgcn_lstm: AX, h_init and c_init are constants (no gradient is formed for them)");
+  return WdgcnLstmFn::apply(AX, P, h0, c0, H, T_run, grad && P.requires_grad());
+}
 Tensor weighted_ce_ad(const Tensor& logits, const Tensor& target, const Tensor& weight, int64_t ignore_index) {
   return WeightedCeFn::apply(logits, target, weight, ignore_index);
 }
@@ -1105,6 +1186,10 @@ TORCH_LIBRARY(tmgcn, m) {
         "float weight_decay, bool nesterov, bool maximize, bool first_step) -> (Tensor, Tensor, Tensor)");
   m.def("unit_gradient(Tensor like) -> Tensor");
   m.def("widen_params(Tensor[] params) -> Tensor[]");
+  m.def("wdgcn_fwd(Tensor AX, Tensor P, Tensor h0, Tensor c0, int H, int T_run, bool need_c) -> (Tensor, Tensor)");
+  m.def("wdgcn_bwd(Tensor AX, Tensor P, Tensor h0, Tensor c0, Tensor Z, Tensor C, Tensor dZ) -> Tensor");
+  m.def("wdgcn_supported(int F0, int H) -> bool", &wdgcn_supported);
+  m.def("wdgcn_lstm(Tensor AX, Tensor P, Tensor h0, Tensor c0, int H, int T_run) -> Tensor");
 }
 
 // ROCm tensors carry the CUDA dispatch key in PyTorch-ROCm
@@ -1128,6 +1213,8 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("scale2", &scale2);
   m.impl("sgd_step", &sgd_step);
   m.impl("unit_gradient", &unit_gradient);
+  m.impl("wdgcn_fwd", &wdgcn_fwd);
+  m.impl("wdgcn_bwd", &wdgcn_bwd);
   // below the Autograd key (inference mode, or called from inside another autograd node) the
   // differentiable operators are their plain forwards
   m.impl("m_transform", &m_transform_ad);
@@ -1140,6 +1227,7 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("widen_params", &widen_params_ad);
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
+  m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
 }
 
 TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
@@ -1153,6 +1241,7 @@ TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
   m.impl("widen_params", &widen_params_ad);
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
+  m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
 }
 
 // a CPU tensor reaching a kernel-level op gets the reference-style RuntimeError, not "no kernel"
@@ -1175,4 +1264,5 @@ TORCH_LIBRARY_IMPL(tmgcn, CPU, m) {
   m.impl("widen_params", &widen_params_ad);
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
+  m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
 }

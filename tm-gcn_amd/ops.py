@@ -693,3 +693,54 @@ def activation(x: torch.Tensor, act) -> torch.Tensor:
     if _registered():
         return kernels.ops.activation(x, _lib.ACT_IDS[act])
     return _Activation.apply(x, act)
+
+
+# ---- WD-GCN (wd_gcn_functions.py, "wgf") ----------------------------------------------------------------------------
+WDGCN_PARAM_NAMES = ("W", "Wf", "Wj", "Wc", "Wo", "Uf", "Uj", "Uc", "Uo", "bf", "bj", "bc", "bo")   # wgf:36-51, in order
+
+
+@functools.lru_cache(maxsize=None)
+def _wdgcn_widths_ok(F0: int, H: int) -> bool:
+    return bool(_lib.load().tmgcn_wdgcn_supported(F0, H))
+
+
+def wdgcn_supported(F0: int, H: int) -> bool:
+    """True when the fused WD-GCN kernels (csrc/wdgcn.hip) cover the widths: 1 <= F0 <= 8, 1 <= H <= 8."""
+    return kernels.name == "hip" and _wdgcn_widths_ok(int(F0), int(H))
+
+
+def wdgcn_lstm_torch(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tensor) -> torch.Tensor:
+    """The reference's statements (wgf:70, 86-98) as torch operators on the tensors' device: the path of widths the
+    kernels do not cover, and the naive port the kernels are measured against (tools/wdgcn_epoch.py)."""
+    W, Wf, Wj, Wc, Wo, Uf, Uj, Uc, Uo, bf, bj, bc, bo = params
+    Y = torch.relu(torch.matmul(AX, W))
+    N = AX.shape[1]
+    c, h = c0.repeat(N, 1), h0.repeat(N, 1)
+    Z = []
+    for t in range(Y.shape[0]):
+        f = torch.sigmoid(torch.matmul(Y[t], Wf) + torch.matmul(h, Uf) + bf.repeat(N, 1))
+        j = torch.sigmoid(torch.matmul(Y[t], Wj) + torch.matmul(h, Uj) + bj.repeat(N, 1))
+        o = torch.sigmoid(torch.matmul(Y[t], Wo) + torch.matmul(h, Uo) + bo.repeat(N, 1))
+        ct = torch.sigmoid(torch.matmul(Y[t], Wc) + torch.matmul(h, Uc) + bc.repeat(N, 1))
+        c = j * ct + f * c
+        h = o * torch.tanh(c)
+        Z.append(h)
+    return torch.stack(Z) if Z else AX.new_zeros(0, N, W.shape[-1])
+
+
+def wdgcn_lstm(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tensor, T_run: Optional[int] = None) -> torch.Tensor:
+    """Z [T_run, N, H] = LSTM(relu(AX·W)) of WD-GCN (wgf:70, 86-98) over the first T_run slices of AX [T, N, F0]
+    (default: all).  ``params``: the 13 parameters in the reference's order (WDGCN_PARAM_NAMES); h0 / c0: h_init /
+    c_init [H].  One forward launch and two backward launches (csrc/wdgcn.hip; gradients for the parameters only) when
+    wdgcn_supported(F0, H), else the reference's statements as torch operators on the device."""
+    params = list(params)
+    if len(params) != 13:
+        raise RuntimeError(f"wdgcn_lstm: expected the 13 parameters {WDGCN_PARAM_NAMES}, got {len(params)}")
+    F0, H = AX.shape[-1], params[0].shape[-1]
+    T_run = AX.shape[0] if T_run is None else int(T_run)
+    if not 0 <= T_run <= AX.shape[0]:
+        raise RuntimeError(f"wdgcn_lstm: T_run={T_run} outside 0..{AX.shape[0]}")
+    if not wdgcn_supported(F0, H):
+        return wdgcn_lstm_torch(AX[:T_run], params, h0, c0)
+    P = torch.cat([p.reshape(-1) for p in params])
+    return kernels.ops.wdgcn_lstm(_want(AX, "wdgcn_lstm AX"), P, h0.contiguous(), c0.contiguous(), H, T_run)
