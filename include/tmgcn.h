@@ -44,7 +44,8 @@ typedef enum {
 /* activation ids for the fused P3 epilogue / P5 pointwise (ehf:284-289, 455-460) */
 enum { TMGCN_ACT_NONE = 0, TMGCN_ACT_RELU = 1, TMGCN_ACT_LEAKY = 2, TMGCN_ACT_SELU = 3 };
 
-/* Additions to ABI version 5 (backward compatible, the version stays 5): the WD-GCN entry points tmgcn_wdgcn_* (below).
+/* Additions to ABI version 5 (backward compatible, the version stays 5): the WD-GCN entry points tmgcn_wdgcn_* and the
+ * EvolveGCN-H entry points tmgcn_egcn_* (below).
  * ABI version 5 = version 4 + tmgcn_pool_stats + the row_blocks partition argument of tmgcn_layer12_fwd/bwd_f32, the backward's AX / dW2 pair and tmgcn_layer12_bwd_forms_dw2 + tmgcn_head_loss_combine_f32 / tmgcn_head_loss_lanes (split rows of the one-pass head + loss plan) + the giant-row
  *   plan entry points tmgcn_spmm_csr_batched_f32_plan / tmgcn_spmm_gemm_f32_plan / tmgcn_spmm_giant_workspace_bytes; the launchers' scratch words (tile counters, hand-off blocks) are kept apart
  *   per stream (eager launches) and per recorded launch (hipGraph capture), and a launcher that cannot keep two launches
@@ -504,6 +505,47 @@ int64_t tmgcn_wdgcn_bwd_workspace_bytes(int64_t N, int32_t F0, int32_t H);
 int tmgcn_wdgcn_bwd_f32(const float* AX, const float* P, const float* h0, const float* c0, const float* Z,
                         const float* C, const float* dZ, float* dP, int64_t N, int32_t T_run, int32_t F0,
                         int32_t H, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- EvolveGCN-H: top-k summary + matrix-GRU weight evolution of one layer (additions to ABI 5) --------------
+ * TensorGCN-master/evolvegcn_functions.py ("ef"), EvolveGCN_1_layer / EvolveGCN_2_layer / EvolveGCN_reg:
+ *   for t = 0..T_run-1 (ef:67-69, 165-169):
+ *     y = H_t·p/‖p‖   idx = topk(y, k)   Zs = H_t[idx]·y[idx]                         ef:80-84
+ *     X = Zsᵀ [F][k], W = W_t-1:  Z = σ(W_Z X + U_Z W + B_Z)  R = σ(W_R X + U_R W + B_R)
+ *     Ĥ = tanh(W_H X + U_H (R∘W) + B_H)   W_t = (1−Z)∘W + Z∘Ĥ                      ef:86-91, 93-95
+ * H [>= T_run][N][F] fp32 (only the first T_run slices are read), k = the width of W (F_next).  Scores, summary and GRU
+ * are fp64.  P: p and the nine gate matrices packed in the reference's draw order (ef:37-46), fp64,
+ * tmgcn_egcn_param_count(F, k) values:  p [F] | W_Z U_Z [F][F] B_Z [F][k] | W_R U_R [F][F] B_R [F][k] | W_H U_H B_H.
+ * W0 [F][k] fp64: W_init.  Supported when tmgcn_egcn_supported(F, k): 1 <= F <= 8, 1 <= k <= 8; N >= k when T_run > 0.
+ * TIE RULE of the top-k: a higher score ranks first; EQUAL scores rank by the LOWER node index; a NaN score is never
+ *   selected (a slice with fewer than k non-NaN scores gets idx = -1, y_sel = 0 and a zero column in the unfilled
+ *   places).  The result does not depend on the block count or the run.
+ * Forward (replaces the Python loop ef:67-71 / 165-171 up to the GCONV): idx [T_run][k] int32, y_sel [T_run][k], the
+ *   selected rows H_sel [T_run][k][F] and X_g [T_run][F][k] (= Zsᵀ) fp64, W_seq [T_run+1][F][k] fp64 (W_seq[0] = W0,
+ *   W_seq[t+1] = W_t), W32 [T_run][F][k] = (float)W_seq[1:] for the GEMMs, gates [T_run][3][F][k] (Z, R, Ĥ of every
+ *   step; NULL when no backward follows).  workspace >= tmgcn_egcn_fwd_workspace_bytes(N, T_run, F, k).
+ *   T_run == 0: only W_seq[0] = W0 is written.
+ * Layer 2 (rowptr not NULL): H is relu(Â_t·X_prev_t·W_prev_t) of the layer below, in fp32 as the GCONV uses it; the
+ *   ranking uses it, and the k selected rows are formed again in fp64 (ef:168 with the reference's fp64 operands) from
+ *   the batched CSR of Â (rowptr [>= T_run·N + 1] int64, col int32, val fp32 — csr.py; col and val may be NULL when
+ *   the CSR holds no entries, they are read for a selected row's entries only), X_prev [>= T_run][N][F_prev] fp32 and
+ *   W_prev = that layer's W_seq [T_run+1][F_prev][F] fp64, any F_prev >= 1.  rowptr NULL: the rows of H itself.
+ * Backward (autograd of the statements above, from the forward's X_g, idx, y_sel, H_sel, W_seq, gates): dW32 [T_run][F][k] fp32 (the GEMMs' per-slice dW) and dWseq
+ *   [T_run+1][F][k] fp64 (the gradient of W_seq, e.g. of the returned W_T) are added at each step (either may be NULL);
+ *   out: dP (packed like P), dW0 [F][k], and, when dH is not NULL, dH [T_run][N][F] fp32 = the summary's gradient with
+ *   respect to H (zero outside the selected rows).  No atomics: fixed summation order, the same bits on every run.
+ *   workspace >= tmgcn_egcn_bwd_workspace_bytes(T_run, F, k). */
+int tmgcn_egcn_supported(int32_t F, int32_t k);
+int64_t tmgcn_egcn_param_count(int32_t F, int32_t k);
+int64_t tmgcn_egcn_fwd_workspace_bytes(int64_t N, int32_t T_run, int32_t F, int32_t k);
+int tmgcn_egcn_fwd(const float* H, const double* P, const double* W0, const int64_t* rowptr, const int32_t* col,
+                   const float* val, const float* X_prev, const double* W_prev, int32_t F_prev, int32_t* idx,
+                   double* y_sel, double* H_sel, double* X_g, double* W_seq, float* W32, double* gates, int64_t N,
+                   int32_t T_run, int32_t F, int32_t k, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t tmgcn_egcn_bwd_workspace_bytes(int32_t T_run, int32_t F, int32_t k);
+int tmgcn_egcn_bwd(const double* P, const double* X_g, const int32_t* idx, const double* y_sel, const double* H_sel,
+                   const double* W_seq, const double* gates, const float* dW32, const double* dWseq, double* dP,
+                   double* dW0, float* dH, int64_t N, int32_t T_run, int32_t F, int32_t k, void* workspace,
+                   int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,9 +14,10 @@
 //     tmgcn::act_fwd/bwd         tmgcn_act_*_f32                   ehf:284-289
 //     tmgcn::wce_fwd/bwd         tmgcn_wce_*_f32                   experiment_reddit_our_link_prediction.py:69, 79
 //     tmgcn::wdgcn_fwd/bwd       tmgcn_wdgcn_*_f32                 wd_gcn_functions.py:70, 86-98 (WD-GCN)
+//     tmgcn::egcn_fwd/bwd        tmgcn_egcn_fwd / _bwd             evolvegcn_functions.py:80-95 (EvolveGCN-H)
 //   differentiable ops (registered under the Autograd key)
 //     tmgcn::m_transform, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm,
-//     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce, tmgcn::wdgcn_lstm
+//     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce, tmgcn::wdgcn_lstm, tmgcn::egcn_evolve
 //
 // No kernels live here: every launch goes through the C-ABI shared library (libtmgcn_hip.so),
 // on torch's current HIP stream.  Errors surface as RuntimeError (TORCH_CHECK), the reference's
@@ -675,6 +676,133 @@ Tensor wdgcn_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tens
   return dP.view(P.sizes());
 }
 
+// ---- EvolveGCN-H (evolvegcn_functions.py:80-95): top-k summary + matrix-GRU weight evolution, and its backward ------
+bool egcn_supported(int64_t F, int64_t k) { return tmgcn_egcn_supported((int32_t)F, (int32_t)k) != 0; }
+
+static void egcn_check(const Tensor& H, const Tensor& P, const Tensor& W0, int64_t k, int64_t T_run) {
+  want(H, "egcn H");
+  want(P, "egcn P", at::kDouble);
+  want(W0, "egcn W_init", at::kDouble);
+  TORCH_CHECK(H.dim() == 3, "egcn: H must be [T, N, F], got ", H.sizes());
+  const int64_t F = H.size(2), N = H.size(1);
+  TORCH_CHECK(tmgcn_egcn_supported((int32_t)F, (int32_t)k), "egcn: F=", F, ", k=", k,
+              " outside the kernel's widths (1..8 each)");
+  TORCH_CHECK(T_run >= 0 && T_run <= H.size(0), "egcn: T_run=", T_run, " outside 0..", H.size(0));
+  TORCH_CHECK(T_run == 0 || N >= k, "egcn: topk needs N >= k (N=", N, ", k=", k, ")");
+  TORCH_CHECK(P.numel() == tmgcn_egcn_param_count((int32_t)F, (int32_t)k), "egcn: P holds ", P.numel(),
+              " values, the packed parameters of F=", F, ", k=", k, " are ", tmgcn_egcn_param_count((int32_t)F, (int32_t)k));
+  TORCH_CHECK(W0.numel() == F * k, "egcn: W_init must be [F=", F, ", k=", k, "], got ", W0.sizes());
+  TORCH_CHECK(H.device() == P.device() && H.device() == W0.device(), "egcn: H, P and W_init must be on one device");
+}
+
+// layer 2's fp64 rows (tmgcn.h): the batched CSR of Â, X_prev [>= T_run, N, F_prev] and W_prev [T_run+1, F_prev, F]
+struct EgcnRows {
+  const int64_t* rowptr = nullptr;
+  const int32_t* col = nullptr;
+  const float* val = nullptr;
+  const float* X = nullptr;
+  const double* W = nullptr;
+  int32_t F_prev = 0;
+};
+static EgcnRows egcn_rows(const Tensor& H, int64_t T_run, const OptTensor& rowptr, const OptTensor& col,
+                          const OptTensor& val, const OptTensor& Xp, const OptTensor& Wp) {
+  EgcnRows r;
+  if (!rowptr.has_value() || !rowptr->defined()) return r;
+  TORCH_CHECK(col.has_value() && val.has_value() && Xp.has_value() && Wp.has_value(),
+              "egcn: the fp64 rows of layer 2 need rowptr, col, val, X_prev and W_prev together");
+  const int64_t N = H.size(1), F = H.size(2);
+  want(*rowptr, "egcn rowptr", at::kLong);
+  want(*col, "egcn col", at::kInt);
+  want(*val, "egcn val");
+  want(*Xp, "egcn X_prev");
+  want(*Wp, "egcn W_prev", at::kDouble);
+  TORCH_CHECK(Xp->dim() == 3 && Xp->size(0) >= T_run && Xp->size(1) == N, "egcn: X_prev ", Xp->sizes(),
+              " must be [>= T_run=", T_run, ", N=", N, ", F_prev]");
+  const int64_t Fp = Xp->size(2);
+  TORCH_CHECK(Wp->dim() == 3 && Wp->size(0) == T_run + 1 && Wp->size(1) == Fp && Wp->size(2) == F, "egcn: W_prev ",
+              Wp->sizes(), " must be [T_run+1=", T_run + 1, ", F_prev=", Fp, ", F=", F, "]");
+  TORCH_CHECK(rowptr->numel() >= T_run * N + 1 && col->numel() == val->numel(), "egcn: the CSR (rowptr ",
+              rowptr->numel(), ", col ", col->numel(), ", val ", val->numel(), ") does not cover ", T_run, " slices of N=", N);
+  r.rowptr = (const int64_t*)ptr(*rowptr);
+  r.col = (const int32_t*)ptr(*col);                 // NULL for an adjacency without entries: never read then
+  r.val = (const float*)ptr(*val);
+  r.X = (const float*)ptr(*Xp);
+  r.W = (const double*)ptr(*Wp);
+  r.F_prev = (int32_t)Fp;
+  return r;
+}
+
+// (W_seq [T_run+1,F,k] fp64, W32 [T_run,F,k], idx [T_run,k] int32, y_sel [T_run,k], H_sel [T_run,k,F], X_g [T_run,F,k],
+//  gates [T_run,3,F,k])
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egcn_fwd(
+    const Tensor& H, const Tensor& P, const Tensor& W0, int64_t k, int64_t T_run, bool need_gates, const OptTensor& rowptr,
+    const OptTensor& col, const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
+  egcn_check(H, P, W0, k, T_run);
+  const EgcnRows rows = egcn_rows(H, T_run, rowptr, col, val, X_prev, W_prev);
+  c10::DeviceGuard g(H.device());
+  const int64_t N = H.size(1), F = H.size(2);
+  auto f64 = P.options();
+  Tensor Wseq = at::empty({T_run + 1, F, k}, f64), W32 = at::empty({T_run, F, k}, H.options());
+  Tensor idx = at::empty({T_run, k}, H.options().dtype(at::kInt)), ysel = at::empty({T_run, k}, f64);
+  Tensor Hsel = at::empty({T_run, k, F}, f64), Xg = at::empty({T_run, F, k}, f64);
+  Tensor gates = need_gates ? at::empty({T_run, 3, F, k}, f64) : none_like(P);
+  const int64_t need = tmgcn_egcn_fwd_workspace_bytes(N, (int32_t)T_run, (int32_t)F, (int32_t)k);
+  Tensor ws = at::empty({need > 0 ? need : 1}, H.options().dtype(at::kByte));
+  ok(tmgcn_egcn_fwd((const float*)ptr(H), (const double*)ptr(P), (const double*)ptr(W0), rows.rowptr, rows.col, rows.val,
+                    rows.X, rows.W, rows.F_prev, (int32_t*)ptr(idx), (double*)ptr(ysel), (double*)ptr(Hsel),
+                    (double*)ptr(Xg), (double*)ptr(Wseq), (float*)ptr(W32), need_gates ? (double*)ptr(gates) : nullptr, N,
+                    (int32_t)T_run, (int32_t)F, (int32_t)k, ptr(ws), ws.numel(), stream_of(H)),
+     "tmgcn_egcn_fwd");
+  return {Wseq, W32, idx, ysel, Hsel, Xg, gates};
+}
+
+// (dP, dW0, dH) from the gradients of W_seq (fp64, may be undefined) and of W32 (fp32, may be undefined)
+std::tuple<Tensor, Tensor, Tensor> egcn_bwd(const Tensor& H, const Tensor& P, const Tensor& W0, const Tensor& Xg,
+                                            const Tensor& idx, const Tensor& ysel, const Tensor& Hsel, const Tensor& Wseq,
+                                            const Tensor& gates, const OptTensor& dWseq_, const OptTensor& dW32_,
+                                            bool need_dH) {
+  const int64_t T_run = Wseq.dim() == 3 ? Wseq.size(0) - 1 : -1, k = Wseq.dim() == 3 ? Wseq.size(2) : -1;
+  egcn_check(H, P, W0, k, T_run);
+  const int64_t N = H.size(1), F = H.size(2);
+  want(Wseq, "egcn W_seq", at::kDouble);
+  TORCH_CHECK(Wseq.size(1) == F, "egcn_bwd: W_seq ", Wseq.sizes(), " does not match F=", F);
+  if (T_run > 0) {
+    want(Xg, "egcn X_g", at::kDouble);
+    want(idx, "egcn idx", at::kInt);
+    want(ysel, "egcn y_sel", at::kDouble);
+    want(Hsel, "egcn H_sel", at::kDouble);
+    want(gates, "egcn gates", at::kDouble);
+    TORCH_CHECK(Xg.numel() == T_run * F * k && idx.numel() == T_run * k && ysel.numel() == T_run * k &&
+                    Hsel.numel() == T_run * k * F && gates.numel() == T_run * 3 * F * k,
+                "egcn_bwd: the saved forward tensors do not match T_run=", T_run, ", F=", F, ", k=", k);
+  }
+  Tensor dWseq, dW32;
+  if (dWseq_.has_value() && dWseq_->defined()) {
+    dWseq = dWseq_->contiguous();
+    want(dWseq, "egcn dW_seq", at::kDouble);
+    TORCH_CHECK(dWseq.sizes() == Wseq.sizes(), "egcn_bwd: dW_seq ", dWseq.sizes(), " must be ", Wseq.sizes());
+  }
+  if (dW32_.has_value() && dW32_->defined()) {
+    dW32 = dW32_->contiguous();
+    want(dW32, "egcn dW32");
+    TORCH_CHECK(dW32.numel() == T_run * F * k, "egcn_bwd: dW32 ", dW32.sizes(), " must be [", T_run, ", ", F, ", ", k, "]");
+  }
+  c10::DeviceGuard g(H.device());
+  Tensor dP = at::empty({P.numel()}, P.options()), dW0 = at::empty({F, k}, P.options());
+  Tensor dH = need_dH ? (H.size(0) == T_run ? at::empty(H.sizes(), H.options()) : at::zeros(H.sizes(), H.options()))
+                      : Tensor();
+  const int64_t need = tmgcn_egcn_bwd_workspace_bytes((int32_t)T_run, (int32_t)F, (int32_t)k);
+  Tensor ws = at::empty({need > 0 ? need : 1}, H.options().dtype(at::kByte));
+  ok(tmgcn_egcn_bwd((const double*)ptr(P), (const double*)ptr(Xg), (const int32_t*)ptr(idx), (const double*)ptr(ysel),
+                    (const double*)ptr(Hsel), (const double*)ptr(Wseq), (const double*)ptr(gates),
+                    dW32.defined() ? (const float*)ptr(dW32) : nullptr,
+                    dWseq.defined() ? (const double*)ptr(dWseq) : nullptr, (double*)ptr(dP), (double*)ptr(dW0),
+                    need_dH ? (float*)ptr(dH) : nullptr, N, (int32_t)T_run, (int32_t)F, (int32_t)k, ptr(ws), ws.numel(),
+                    stream_of(H)),
+     "tmgcn_egcn_bwd");
+  return {dP, dW0.view(W0.sizes()), dH};
+}
+
 bool edge_head_supported(int64_t F, int64_t C) { return tmgcn_edge_head_supported((int32_t)F, (int32_t)C) != 0; }
 bool head_loss_supported(int64_t F, int64_t C, int64_t K) { return tmgcn_head_loss_supported((int32_t)F, (int32_t)C, (int32_t)K) != 0; }
 int64_t abi_version() { return tmgcn_abi_version(); }
@@ -1042,6 +1170,58 @@ struct WdgcnLstmFn : public torch::autograd::Function<WdgcnLstmFn> {
   }
 };
 
+// the weight evolution of one EvolveGCN-H layer: (W_seq fp64 [T_run+1,F,k], W32 = W_seq[1:] in fp32 for the GEMMs);
+// gradients for p, the nine gate matrices, W_init and (when it requires one: layer 2) H
+struct EgcnEvolveFn : public torch::autograd::Function<EgcnEvolveFn> {
+  static variable_list forward(AutogradContext* ctx, const Tensor& H, const Tensor& p, at::TensorList gates,
+                               const Tensor& W0, at::TensorList rows, int64_t k, int64_t T_run, bool need,
+                               bool need_dH) {
+    // rows: empty, or layer 2's (rowptr, col, val, X_prev, W_prev)
+    at::AutoDispatchBelowADInplaceOrView guard;
+    std::vector<Tensor> parts{p.reshape({-1})};
+    for (const Tensor& q : gates) parts.push_back(q.reshape({-1}));
+    Tensor P = at::cat(parts).contiguous();
+    Tensor W0c = W0.contiguous();
+    auto opt = [&](size_t i) { return i < rows.size() ? OptTensor(rows[i]) : OptTensor(); };
+    auto [Wseq, W32, idx, ysel, Hsel, Xg, gt] = egcn_fwd(H, P, W0c, k, T_run, need, opt(0), opt(1), opt(2), opt(3), opt(4));
+    if (need) {
+      ctx->save_for_backward({H, P, W0c, Xg, idx, ysel, Hsel, Wseq, gt});
+      ctx->saved_data["need_dH"] = need_dH;
+      ctx->saved_data["n_gates"] = (int64_t)gates.size();
+      ctx->saved_data["n_rows"] = (int64_t)rows.size();
+      ctx->saved_data["p_numel"] = p.numel();
+      ctx->saved_data["p_shape"] = p.sizes().vec();
+      for (size_t i = 0; i < gates.size(); ++i) ctx->saved_data["g" + std::to_string(i)] = gates[i].sizes().vec();
+    }
+    return {Wseq, W32};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    auto sv = ctx->get_saved_variables();
+    const bool need_dH = ctx->saved_data["need_dH"].toBool();
+    auto [dP, dW0, dH] = egcn_bwd(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7], sv[8], grads[0], grads[1], need_dH);
+    const int64_t n_gates = ctx->saved_data["n_gates"].toInt();
+    variable_list out;
+    out.push_back(need_dH ? dH : Tensor());
+    int64_t off = 0;
+    auto take = [&](const std::vector<int64_t>& shape) {
+      int64_t n = 1;
+      for (int64_t d : shape) n *= d;
+      Tensor v = dP.narrow(0, off, n).view(shape);
+      off += n;
+      return v;
+    };
+    out.push_back(take(ctx->saved_data["p_shape"].toIntVector()));
+    for (int64_t i = 0; i < n_gates; ++i) out.push_back(take(ctx->saved_data["g" + std::to_string(i)].toIntVector()));
+    out.push_back(dW0);
+    // rows: the gradient of layer 2's fp64 rows reaches W_prev through dH and the GCONV that formed H; then k, T_run,
+    // need, need_dH
+    const int64_t n_rows = ctx->saved_data["n_rows"].toInt();
+    for (int64_t i = 0; i < n_rows + 4; ++i) out.push_back(Tensor());
+    return out;
+  }
+};
+
 struct ActivationFn : public torch::autograd::Function<ActivationFn> {
   static Tensor forward(AutogradContext* ctx, const Tensor& x, int64_t act) {
     at::AutoDispatchBelowADInplaceOrView guard;
@@ -1122,6 +1302,23 @@ Tensor wdgcn_lstm_ad(const Tensor& AX, const Tensor& P, const Tensor& h0, const 
               "wdgcn_lstm: AX, h_init and c_init are constants (no gradient is formed for them)");
   return WdgcnLstmFn::apply(AX, P, h0, c0, H, T_run, grad && P.requires_grad());
 }
+std::tuple<Tensor, Tensor> egcn_evolve_ad(const Tensor& H, const Tensor& p, at::TensorList gates, const Tensor& W0,
+                                          int64_t k, int64_t T_run, const OptTensor& rowptr, const OptTensor& col,
+                                          const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
+  TORCH_CHECK(gates.size() == 9, "egcn_evolve: expected the nine gate matrices W_Z U_Z B_Z W_R U_R B_R W_H U_H B_H, got ",
+              gates.size());
+  const bool grad = at::GradMode::is_enabled();
+  bool any = p.requires_grad() || W0.requires_grad() || H.requires_grad();
+  for (const Tensor& q : gates) any = any || q.requires_grad();
+  std::vector<Tensor> rows;
+  if (rowptr.has_value() && rowptr->defined()) {
+    TORCH_CHECK(col.has_value() && val.has_value() && X_prev.has_value() && W_prev.has_value(),
+                "egcn_evolve: the fp64 rows of layer 2 need rowptr, col, val, X_prev and W_prev together");
+    rows = {*rowptr, *col, *val, *X_prev, *W_prev};
+  }
+  auto r = EgcnEvolveFn::apply(H, p, gates, W0, at::TensorList(rows), k, T_run, grad && any, grad && H.requires_grad());
+  return {r[0], r[1]};
+}
 Tensor weighted_ce_ad(const Tensor& logits, const Tensor& target, const Tensor& weight, int64_t ignore_index) {
   return WeightedCeFn::apply(logits, target, weight, ignore_index);
 }
@@ -1190,6 +1387,13 @@ TORCH_LIBRARY(tmgcn, m) {
   m.def("wdgcn_bwd(Tensor AX, Tensor P, Tensor h0, Tensor c0, Tensor Z, Tensor C, Tensor dZ) -> Tensor");
   m.def("wdgcn_supported(int F0, int H) -> bool", &wdgcn_supported);
   m.def("wdgcn_lstm(Tensor AX, Tensor P, Tensor h0, Tensor c0, int H, int T_run) -> Tensor");
+  m.def("egcn_fwd(Tensor H, Tensor P, Tensor W0, int k, int T_run, bool need_gates, Tensor? rowptr=None, Tensor? col=None, "
+        "Tensor? val=None, Tensor? X_prev=None, Tensor? W_prev=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("egcn_bwd(Tensor H, Tensor P, Tensor W0, Tensor X_g, Tensor idx, Tensor y_sel, Tensor H_sel, Tensor W_seq, "
+        "Tensor gates, Tensor? dW_seq, Tensor? dW32, bool need_dH) -> (Tensor, Tensor, Tensor)");
+  m.def("egcn_supported(int F, int k) -> bool", &egcn_supported);
+  m.def("egcn_evolve(Tensor H, Tensor p, Tensor[] gate_params, Tensor W_init, int k, int T_run, Tensor? rowptr=None, "
+        "Tensor? col=None, Tensor? val=None, Tensor? X_prev=None, Tensor? W_prev=None) -> (Tensor, Tensor)");
 }
 
 // ROCm tensors carry the CUDA dispatch key in PyTorch-ROCm
@@ -1215,6 +1419,8 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("unit_gradient", &unit_gradient);
   m.impl("wdgcn_fwd", &wdgcn_fwd);
   m.impl("wdgcn_bwd", &wdgcn_bwd);
+  m.impl("egcn_fwd", &egcn_fwd);
+  m.impl("egcn_bwd", &egcn_bwd);
   // below the Autograd key (inference mode, or called from inside another autograd node) the
   // differentiable operators are their plain forwards
   m.impl("m_transform", &m_transform_ad);
@@ -1228,6 +1434,7 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
+  m.impl("egcn_evolve", &egcn_evolve_ad);
 }
 
 TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
@@ -1242,6 +1449,7 @@ TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
+  m.impl("egcn_evolve", &egcn_evolve_ad);
 }
 
 // a CPU tensor reaching a kernel-level op gets the reference-style RuntimeError, not "no kernel"
@@ -1265,4 +1473,5 @@ TORCH_LIBRARY_IMPL(tmgcn, CPU, m) {
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
+  m.impl("egcn_evolve", &egcn_evolve_ad);
 }

@@ -744,3 +744,68 @@ def wdgcn_lstm(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tensor, T_r
         return wdgcn_lstm_torch(AX[:T_run], params, h0, c0)
     P = torch.cat([p.reshape(-1) for p in params])
     return kernels.ops.wdgcn_lstm(_want(AX, "wdgcn_lstm AX"), P, h0.contiguous(), c0.contiguous(), H, T_run)
+
+
+# ---- EvolveGCN-H (evolvegcn_functions.py, "ef") ---------------------------------------------------------------------
+EGCN_GATE_NAMES = ("W_Z", "U_Z", "B_Z", "W_R", "U_R", "B_R", "W_H", "U_H", "B_H")    # ef:38-46, in order
+
+
+@functools.lru_cache(maxsize=None)
+def _egcn_widths_ok(F: int, k: int) -> bool:
+    return bool(_lib.load().tmgcn_egcn_supported(F, k))
+
+
+def egcn_supported(F: int, k: int) -> bool:
+    """True when the EvolveGCN-H kernels (csrc/evolvegcn.hip) cover the widths: 1 <= F <= 8, 1 <= k <= 8."""
+    return kernels.name == "hip" and _egcn_widths_ok(int(F), int(k))
+
+
+def egcn_evolve_torch(H: torch.Tensor, p: torch.Tensor, gates, W_init: torch.Tensor, T_run: Optional[int] = None):
+    """The weight evolution of ef:80-95 as torch operators on the tensors' device: the path of widths the kernels do not
+    cover, and the naive port they are measured against (tools/evolvegcn_epoch.py).  Returns (W_seq, W32) like
+    egcn_evolve; torch.topk's order of equal scores is its own."""
+    wz, uz, bz, wr, ur, br, wh, uh, bh = gates
+    T_run = H.shape[0] if T_run is None else int(T_run)
+    k = W_init.shape[1]
+    inv_norm = 1.0 / torch.linalg.vector_norm(p)
+    W = W_init
+    seq = [W]
+    for t in range(T_run):
+        rows = H[t].double()
+        score = (rows @ p) * inv_norm                                               # summary: scores, top k, scaled rows
+        sel = score.topk(k).indices
+        Xg = (rows[sel] * score[sel].unsqueeze(1)).t()                               # [F, k]
+        z = torch.sigmoid(wz @ Xg + uz @ W + bz)                                     # the GRU on matrices
+        r = torch.sigmoid(wr @ Xg + ur @ W + br)
+        cand = torch.tanh(wh @ Xg + uh @ (r * W) + bh)
+        W = W + z * (cand - W)
+        seq.append(W)
+    W_seq = torch.stack(seq)
+    return W_seq, W_seq[1:].float()
+
+
+def egcn_evolve(H: torch.Tensor, p: torch.Tensor, gates, W_init: torch.Tensor, T_run: Optional[int] = None, rows=None):
+    """The weight evolution of one EvolveGCN-H layer over the first T_run slices of H [T, N, F] (default: all):
+    (W_seq [T_run+1, F, k] fp64 with W_seq[0] = W_init and W_seq[t+1] = W_t, W32 = W_seq[1:] in fp32 for the batched
+    GCONV).  ``gates``: the nine matrices in the reference's order (EGCN_GATE_NAMES); p, the gates and W_init fp64.
+    ``rows`` = (A, X_prev, W_prev_seq) for layer 2, whose H = relu(Â_t·X_prev_t·W_prev_t) is fp32: the selected rows
+    are formed again in fp64 from them (include/tmgcn.h), the ranking stays that of H.
+    Three forward launches (summary, merge, chain) and two backward launches (chain BPTT, parameter sums + the summary's
+    backward) when egcn_supported(F, k), else the reference's statements as torch operators on the device.  Gradients
+    for p, the gates, W_init, and H when H requires one (layer 2)."""
+    gates = list(gates)
+    if len(gates) != 9:
+        raise RuntimeError(f"egcn_evolve: expected the nine gate matrices {EGCN_GATE_NAMES}, got {len(gates)}")
+    F, k = H.shape[-1], W_init.shape[-1]
+    T_run = H.shape[0] if T_run is None else int(T_run)
+    if not 0 <= T_run <= H.shape[0]:
+        raise RuntimeError(f"egcn_evolve: T_run={T_run} outside 0..{H.shape[0]}")
+    if T_run and H.shape[1] < k:
+        raise RuntimeError(f"egcn_evolve: topk needs N >= k (N={H.shape[1]}, k={k}) (ef:82)")
+    if not egcn_supported(F, k):
+        return egcn_evolve_torch(H, p, gates, W_init, T_run)
+    if rows is not None:
+        A, Xp, Wp = rows
+        return kernels.ops.egcn_evolve(_want(H, "egcn_evolve H"), p, gates, W_init, k, T_run, A.rowptr, A.col, A.val,
+                                       _want(Xp, "egcn_evolve X_prev"), Wp)
+    return kernels.ops.egcn_evolve(_want(H, "egcn_evolve H"), p, gates, W_init, k, T_run)
