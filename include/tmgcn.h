@@ -44,8 +44,8 @@ typedef enum {
 /* activation ids for the fused P3 epilogue / P5 pointwise (ehf:284-289, 455-460) */
 enum { TMGCN_ACT_NONE = 0, TMGCN_ACT_RELU = 1, TMGCN_ACT_LEAKY = 2, TMGCN_ACT_SELU = 3 };
 
-/* Additions to ABI version 5 (backward compatible, the version stays 5): the WD-GCN entry points tmgcn_wdgcn_* and the
- * EvolveGCN-H entry points tmgcn_egcn_* (below).
+/* Additions to ABI version 5 (backward compatible, the version stays 5): the WD-GCN entry points tmgcn_wdgcn_*, their
+ * wide counterparts tmgcn_wdgcn_wide_* (widths up to 64) and the EvolveGCN-H entry points tmgcn_egcn_* (below).
  * ABI version 5 = version 4 + tmgcn_pool_stats + the row_blocks partition argument of tmgcn_layer12_fwd/bwd_f32, the backward's AX / dW2 pair and tmgcn_layer12_bwd_forms_dw2 + tmgcn_head_loss_combine_f32 / tmgcn_head_loss_lanes (split rows of the one-pass head + loss plan) + the giant-row
  *   plan entry points tmgcn_spmm_csr_batched_f32_plan / tmgcn_spmm_gemm_f32_plan / tmgcn_spmm_giant_workspace_bytes; the launchers' scratch words (tile counters, hand-off blocks) are kept apart
  *   per stream (eager launches) and per recorded launch (hipGraph capture), and a launcher that cannot keep two launches
@@ -505,6 +505,32 @@ int64_t tmgcn_wdgcn_bwd_workspace_bytes(int64_t N, int32_t F0, int32_t H);
 int tmgcn_wdgcn_bwd_f32(const float* AX, const float* P, const float* h0, const float* c0, const float* Z,
                         const float* C, const float* dZ, float* dP, int64_t N, int32_t T_run, int32_t F0,
                         int32_t H, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- WD-GCN at widths up to 64 (additions to ABI 5) ------------------------------------------------------------
+ * The same statements, tensors and packed P as above for the widths the entry points above reject:
+ * tmgcn_wdgcn_wide_supported(F0, H): 1 <= F0 <= 64, 1 <= H <= 64 and not tmgcn_wdgcn_supported(F0, H), so every pair of
+ * widths has exactly one kernel family.  The products run on the exact-f32 matrix cores (v_mfma_f32_16x16x4_f32) with the
+ * weights resident in LDS for all steps; widths that are no multiple of 16 are zero-padded inside the kernels.  The
+ * summation order differs from the narrow kernels' (k in MFMA order), the arithmetic is the same fp32 fma chain.
+ * Forward: one launch for all T_run steps.  saved = NULL: no gradient will be asked for, only Z is written.  Otherwise
+ *   saved (opaque, tmgcn_wdgcn_wide_saved_bytes(N, T_run, F0, H) = 6 · T_run · N · H · 4 bytes) receives, per step, node
+ *   and hidden unit, y = relu(AX·W), the cell state c and the four gate activations f, j, ct, o: the backward reads them
+ *   instead of repeating the forward's products.
+ * Backward (BPTT, gradients for the 13 parameters): three launches — the recurrence (dz of the four gates and
+ *   dy ⊙ relu' per step into the workspace), the parameter gradients as products over the T_run·N rows into per-block
+ *   slabs, and the slabs added in a fixed order in fp64.  No atomics: the same bits on every run.
+ *   workspace >= tmgcn_wdgcn_wide_bwd_workspace_bytes(N, T_run, F0, H): (5 · T_run · N · H + slabs · param_count) · 4.
+ * The size functions return -1 for unsupported widths or negative sizes, 0 for N == 0 or T_run == 0 (the forward is then
+ * a no-op, the backward writes dP = 0).  Arguments are validated before any device work (TMGCN_ERR_INVALID and a
+ * tmgcn_last_error() message); no process-wide state; no host synchronisation and no allocation (capturable). */
+int tmgcn_wdgcn_wide_supported(int32_t F0, int32_t H);
+int64_t tmgcn_wdgcn_wide_saved_bytes(int64_t N, int32_t T_run, int32_t F0, int32_t H);
+int tmgcn_wdgcn_wide_fwd_f32(const float* AX, const float* P, const float* h0, const float* c0, float* Z, void* saved,
+                             int64_t N, int32_t T_run, int32_t F0, int32_t H, void* stream);
+int64_t tmgcn_wdgcn_wide_bwd_workspace_bytes(int64_t N, int32_t T_run, int32_t F0, int32_t H);
+int tmgcn_wdgcn_wide_bwd_f32(const float* AX, const float* P, const float* h0, const float* c0, const float* Z,
+                             const void* saved, const float* dZ, float* dP, int64_t N, int32_t T_run, int32_t F0,
+                             int32_t H, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- EvolveGCN-H: top-k summary + matrix-GRU weight evolution of one layer (additions to ABI 5) --------------
  * TensorGCN-master/evolvegcn_functions.py ("ef"), EvolveGCN_1_layer / EvolveGCN_2_layer / EvolveGCN_reg:

@@ -91,6 +91,11 @@ SIGNATURES = {
     "tmgcn_wdgcn_fwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p]),
     "tmgcn_wdgcn_bwd_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "tmgcn_wdgcn_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _i64, _p]),
+    "tmgcn_wdgcn_wide_supported": (C.c_int, [_i32, _i32]),
+    "tmgcn_wdgcn_wide_saved_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "tmgcn_wdgcn_wide_fwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p]),
+    "tmgcn_wdgcn_wide_bwd_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "tmgcn_wdgcn_wide_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _i64, _p]),
     "tmgcn_egcn_supported": (C.c_int, [_i32, _i32]),
     "tmgcn_egcn_param_count": (_i64, [_i32, _i32]),
     "tmgcn_egcn_fwd_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),

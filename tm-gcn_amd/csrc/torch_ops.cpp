@@ -14,6 +14,7 @@
 //     tmgcn::act_fwd/bwd         tmgcn_act_*_f32                   ehf:284-289
 //     tmgcn::wce_fwd/bwd         tmgcn_wce_*_f32                   experiment_reddit_our_link_prediction.py:69, 79
 //     tmgcn::wdgcn_fwd/bwd       tmgcn_wdgcn_*_f32                 wd_gcn_functions.py:70, 86-98 (WD-GCN)
+//     tmgcn::wdgcn_wide_fwd/bwd  tmgcn_wdgcn_wide_*_f32            the same at widths up to 64 (MFMA kernels)
 //     tmgcn::egcn_fwd/bwd        tmgcn_egcn_fwd / _bwd             evolvegcn_functions.py:80-95 (EvolveGCN-H)
 //   differentiable ops (registered under the Autograd key)
 //     tmgcn::m_transform, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm,
@@ -676,6 +677,69 @@ Tensor wdgcn_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tens
   return dP.view(P.sizes());
 }
 
+// ---- WD-GCN at widths up to 64 (csrc/wdgcn_wide.hip): the same operator, `saved` opaque to the caller ----------------
+bool wdgcn_wide_supported(int64_t F0, int64_t H) { return tmgcn_wdgcn_wide_supported((int32_t)F0, (int32_t)H) != 0; }
+
+static void wdgcn_wide_check(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
+  want(AX, "wdgcn_wide AX");
+  want(P, "wdgcn_wide P");
+  want(h0, "wdgcn_wide h0");
+  want(c0, "wdgcn_wide c0");
+  TORCH_CHECK(AX.dim() == 3, "wdgcn_wide: AX must be [T, N, F0], got ", AX.sizes());
+  const int64_t F0 = AX.size(2);
+  TORCH_CHECK(tmgcn_wdgcn_wide_supported((int32_t)F0, (int32_t)H), "wdgcn_wide: F0=", F0, ", H=", H,
+              " outside the wide kernels' widths (1..64 each, beyond the narrow kernels' 1..8 x 1..8)");
+  TORCH_CHECK(T_run >= 0 && T_run <= AX.size(0), "wdgcn_wide: T_run=", T_run, " outside 0..", AX.size(0));
+  const int64_t np = F0 * H + 8 * H * H + 4 * H;
+  TORCH_CHECK(P.numel() == np, "wdgcn_wide: P holds ", P.numel(), " floats, the packed parameters of F0=", F0, ", H=", H,
+              " are ", np);
+  TORCH_CHECK(h0.numel() == H && c0.numel() == H, "wdgcn_wide: h0 / c0 must hold H=", H, " values");
+}
+
+// Z [T_run, N, H] and, with need_saved, what the backward reads (y, c and the gate activations of every step)
+std::tuple<Tensor, Tensor> wdgcn_wide_fwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H,
+                                          int64_t T_run, bool need_saved) {
+  wdgcn_wide_check(AX, P, h0, c0, H, T_run);
+  c10::DeviceGuard g(AX.device());
+  const int64_t N = AX.size(1), F0 = AX.size(2);
+  Tensor Z = at::empty({T_run, N, H}, AX.options());
+  Tensor saved = none_like(AX);
+  if (need_saved) {
+    const int64_t bytes = tmgcn_wdgcn_wide_saved_bytes(N, (int32_t)T_run, (int32_t)F0, (int32_t)H);
+    TORCH_CHECK(bytes >= 0, "wdgcn_wide_fwd: tmgcn_wdgcn_wide_saved_bytes refused N=", N, ", T_run=", T_run);
+    saved = at::empty({bytes / 4 > 0 ? bytes / 4 : 1}, AX.options());
+  }
+  ok(tmgcn_wdgcn_wide_fwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
+                              (float*)ptr(Z), need_saved ? ptr(saved) : nullptr, N, (int32_t)T_run, (int32_t)F0, (int32_t)H,
+                              stream_of(AX)),
+     "tmgcn_wdgcn_wide_fwd_f32");
+  return {Z, saved};
+}
+
+// dP (packed like P) from dZ [T_run, N, H]
+Tensor wdgcn_wide_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, const Tensor& Z,
+                      const Tensor& saved, const Tensor& dZ) {
+  const int64_t H = Z.dim() == 3 ? Z.size(2) : -1, T_run = Z.dim() == 3 ? Z.size(0) : -1;
+  wdgcn_wide_check(AX, P, h0, c0, H, T_run);
+  want(Z, "wdgcn_wide Z");
+  want(saved, "wdgcn_wide saved");
+  want(dZ, "wdgcn_wide dZ");
+  const int64_t N = AX.size(1), F0 = AX.size(2);
+  TORCH_CHECK(Z.size(1) == N && dZ.sizes() == Z.sizes(), "wdgcn_wide_bwd: Z ", Z.sizes(), ", dZ ", dZ.sizes(),
+              " must both be [T_run, N=", N, ", H]");
+  const int64_t sbytes = tmgcn_wdgcn_wide_saved_bytes(N, (int32_t)T_run, (int32_t)F0, (int32_t)H);
+  TORCH_CHECK(saved.numel() * 4 >= sbytes, "wdgcn_wide_bwd: saved holds ", saved.numel() * 4, " bytes, ", sbytes, " needed");
+  c10::DeviceGuard g(AX.device());
+  Tensor dP = at::empty({P.numel()}, P.options());
+  const int64_t need = tmgcn_wdgcn_wide_bwd_workspace_bytes(N, (int32_t)T_run, (int32_t)F0, (int32_t)H);
+  Tensor ws = at::empty({need > 0 ? need : 1}, AX.options().dtype(at::kByte));
+  ok(tmgcn_wdgcn_wide_bwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
+                              (const float*)ptr(Z), ptr(saved), (const float*)ptr(dZ), (float*)ptr(dP), N, (int32_t)T_run,
+                              (int32_t)F0, (int32_t)H, ptr(ws), ws.numel(), stream_of(AX)),
+     "tmgcn_wdgcn_wide_bwd_f32");
+  return dP.view(P.sizes());
+}
+
 // ---- EvolveGCN-H (evolvegcn_functions.py:80-95): top-k summary + matrix-GRU weight evolution, and its backward ------
 bool egcn_supported(int64_t F, int64_t k) { return tmgcn_egcn_supported((int32_t)F, (int32_t)k) != 0; }
 
@@ -1170,6 +1234,24 @@ struct WdgcnLstmFn : public torch::autograd::Function<WdgcnLstmFn> {
   }
 };
 
+// the same operator through the wide kernels (widths up to 64)
+struct WdgcnWideLstmFn : public torch::autograd::Function<WdgcnWideLstmFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0,
+                        int64_t H, int64_t T_run, bool need) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    auto [Z, saved] = wdgcn_wide_fwd(AX, P, h0, c0, H, T_run, need);
+    if (need) ctx->save_for_backward({AX, P, h0, c0, Z, saved});
+    return Z;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    auto sv = ctx->get_saved_variables();
+    Tensor dZ = grads[0].defined() ? grads[0].contiguous() : at::zeros_like(sv[4]);
+    return {Tensor(), wdgcn_wide_bwd(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], dZ), Tensor(), Tensor(), Tensor(), Tensor(),
+            Tensor()};
+  }
+};
+
 // the weight evolution of one EvolveGCN-H layer: (W_seq fp64 [T_run+1,F,k], W32 = W_seq[1:] in fp32 for the GEMMs);
 // gradients for p, the nine gate matrices, W_init and (when it requires one: layer 2) H
 struct EgcnEvolveFn : public torch::autograd::Function<EgcnEvolveFn> {
@@ -1302,6 +1384,12 @@ Tensor wdgcn_lstm_ad(const Tensor& AX, const Tensor& P, const Tensor& h0, const 
               "wdgcn_lstm: AX, h_init and c_init are constants (no gradient is formed for them)");
   return WdgcnLstmFn::apply(AX, P, h0, c0, H, T_run, grad && P.requires_grad());
 }
+Tensor wdgcn_lstm_wide_ad(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
+  const bool grad = at::GradMode::is_enabled();
+  TORCH_CHECK(!(grad && (AX.requires_grad() || h0.requires_grad() || c0.requires_grad())),
+              "wdgcn_lstm_wide: AX, h_init and c_init are constants (no gradient is formed for them)");
+  return WdgcnWideLstmFn::apply(AX, P, h0, c0, H, T_run, grad && P.requires_grad());
+}
 std::tuple<Tensor, Tensor> egcn_evolve_ad(const Tensor& H, const Tensor& p, at::TensorList gates, const Tensor& W0,
                                           int64_t k, int64_t T_run, const OptTensor& rowptr, const OptTensor& col,
                                           const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
@@ -1387,6 +1475,10 @@ TORCH_LIBRARY(tmgcn, m) {
   m.def("wdgcn_bwd(Tensor AX, Tensor P, Tensor h0, Tensor c0, Tensor Z, Tensor C, Tensor dZ) -> Tensor");
   m.def("wdgcn_supported(int F0, int H) -> bool", &wdgcn_supported);
   m.def("wdgcn_lstm(Tensor AX, Tensor P, Tensor h0, Tensor c0, int H, int T_run) -> Tensor");
+  m.def("wdgcn_wide_fwd(Tensor AX, Tensor P, Tensor h0, Tensor c0, int H, int T_run, bool need_saved) -> (Tensor, Tensor)");
+  m.def("wdgcn_wide_bwd(Tensor AX, Tensor P, Tensor h0, Tensor c0, Tensor Z, Tensor saved, Tensor dZ) -> Tensor");
+  m.def("wdgcn_wide_supported(int F0, int H) -> bool", &wdgcn_wide_supported);
+  m.def("wdgcn_lstm_wide(Tensor AX, Tensor P, Tensor h0, Tensor c0, int H, int T_run) -> Tensor");
   m.def("egcn_fwd(Tensor H, Tensor P, Tensor W0, int k, int T_run, bool need_gates, Tensor? rowptr=None, Tensor? col=None, "
         "Tensor? val=None, Tensor? X_prev=None, Tensor? W_prev=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("egcn_bwd(Tensor H, Tensor P, Tensor W0, Tensor X_g, Tensor idx, Tensor y_sel, Tensor H_sel, Tensor W_seq, "
@@ -1419,6 +1511,8 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("unit_gradient", &unit_gradient);
   m.impl("wdgcn_fwd", &wdgcn_fwd);
   m.impl("wdgcn_bwd", &wdgcn_bwd);
+  m.impl("wdgcn_wide_fwd", &wdgcn_wide_fwd);
+  m.impl("wdgcn_wide_bwd", &wdgcn_wide_bwd);
   m.impl("egcn_fwd", &egcn_fwd);
   m.impl("egcn_bwd", &egcn_bwd);
   // below the Autograd key (inference mode, or called from inside another autograd node) the
@@ -1434,6 +1528,7 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
+  m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
   m.impl("egcn_evolve", &egcn_evolve_ad);
 }
 
@@ -1449,6 +1544,7 @@ TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
+  m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
   m.impl("egcn_evolve", &egcn_evolve_ad);
 }
 
@@ -1473,5 +1569,6 @@ TORCH_LIBRARY_IMPL(tmgcn, CPU, m) {
   m.impl("weighted_ce", &weighted_ce_ad);
   m.impl("head_loss", &head_loss_ad);
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
+  m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
   m.impl("egcn_evolve", &egcn_evolve_ad);
 }

@@ -705,13 +705,35 @@ def _wdgcn_widths_ok(F0: int, H: int) -> bool:
 
 
 def wdgcn_supported(F0: int, H: int) -> bool:
-    """True when the fused WD-GCN kernels (csrc/wdgcn.hip) cover the widths: 1 <= F0 <= 8, 1 <= H <= 8."""
+    """True when the narrow fused WD-GCN kernels (csrc/wdgcn.hip) cover the widths: 1 <= F0 <= 8, 1 <= H <= 8."""
     return kernels.name == "hip" and _wdgcn_widths_ok(int(F0), int(H))
+
+
+@functools.lru_cache(maxsize=None)
+def _wdgcn_wide_widths_ok(F0: int, H: int) -> bool:
+    return bool(_lib.load().tmgcn_wdgcn_wide_supported(F0, H))
+
+
+def wdgcn_wide_supported(F0: int, H: int) -> bool:
+    """True when the wide WD-GCN kernels (csrc/wdgcn_wide.hip, exact-f32 MFMA) cover the widths: 1 <= F0 <= 64,
+    1 <= H <= 64 and not both <= 8 (those belong to the narrow kernels)."""
+    return kernels.name == "hip" and _wdgcn_wide_widths_ok(int(F0), int(H))
+
+
+def wdgcn_lstm_route(F0: int, H: int) -> str:
+    """Which implementation ops.wdgcn_lstm runs at these widths: "narrow" (csrc/wdgcn.hip), "wide"
+    (csrc/wdgcn_wide.hip) or "torch" (wdgcn_lstm_torch: widths beyond 64)."""
+    if wdgcn_supported(F0, H):
+        return "narrow"
+    if wdgcn_wide_supported(F0, H):
+        return "wide"
+    return "torch"
 
 
 def wdgcn_lstm_torch(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tensor) -> torch.Tensor:
     """The reference's statements (wgf:70, 86-98) as torch operators on the tensors' device: the path of widths the
-    kernels do not cover, and the naive port the kernels are measured against (tools/wdgcn_epoch.py)."""
+    kernels do not cover (beyond 64), and the naive port the kernels are measured against (tools/wdgcn_epoch.py,
+    tools/wdgcn_wide_epoch.py)."""
     W, Wf, Wj, Wc, Wo, Uf, Uj, Uc, Uo, bf, bj, bc, bo = params
     Y = torch.relu(torch.matmul(AX, W))
     N = AX.shape[1]
@@ -731,8 +753,10 @@ def wdgcn_lstm_torch(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tenso
 def wdgcn_lstm(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tensor, T_run: Optional[int] = None) -> torch.Tensor:
     """Z [T_run, N, H] = LSTM(relu(AX·W)) of WD-GCN (wgf:70, 86-98) over the first T_run slices of AX [T, N, F0]
     (default: all).  ``params``: the 13 parameters in the reference's order (WDGCN_PARAM_NAMES); h0 / c0: h_init /
-    c_init [H].  One forward launch and two backward launches (csrc/wdgcn.hip; gradients for the parameters only) when
-    wdgcn_supported(F0, H), else the reference's statements as torch operators on the device."""
+    c_init [H].  Dispatched by wdgcn_lstm_route(F0, H): one forward launch and two backward launches of the narrow
+    kernels (csrc/wdgcn.hip) up to 8 x 8, one forward and three backward launches of the MFMA kernels
+    (csrc/wdgcn_wide.hip) up to 64 x 64 (gradients for the parameters only), beyond that the reference's statements
+    as torch operators on the device."""
     params = list(params)
     if len(params) != 13:
         raise RuntimeError(f"wdgcn_lstm: expected the 13 parameters {WDGCN_PARAM_NAMES}, got {len(params)}")
@@ -740,10 +764,12 @@ def wdgcn_lstm(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tensor, T_r
     T_run = AX.shape[0] if T_run is None else int(T_run)
     if not 0 <= T_run <= AX.shape[0]:
         raise RuntimeError(f"wdgcn_lstm: T_run={T_run} outside 0..{AX.shape[0]}")
-    if not wdgcn_supported(F0, H):
+    route = wdgcn_lstm_route(F0, H)
+    if route == "torch":
         return wdgcn_lstm_torch(AX[:T_run], params, h0, c0)
     P = torch.cat([p.reshape(-1) for p in params])
-    return kernels.ops.wdgcn_lstm(_want(AX, "wdgcn_lstm AX"), P, h0.contiguous(), c0.contiguous(), H, T_run)
+    op = kernels.ops.wdgcn_lstm if route == "narrow" else kernels.ops.wdgcn_lstm_wide
+    return op(_want(AX, "wdgcn_lstm AX"), P, h0.contiguous(), c0.contiguous(), H, T_run)
 
 
 # ---- EvolveGCN-H (evolvegcn_functions.py, "ef") ---------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Drop-in WD-GCN modules (TensorGCN-master/wd_gcn_functions.py, "wgf"): the third model family the reference's drivers
-compare (experiment_*_wd-gcn*.py, graph_SEIR_wd_gcn.py), computed by the HIP kernels of csrc/wdgcn.hip.
+compare (experiment_*_wd-gcn*.py, graph_SEIR_wd_gcn.py), computed by the HIP kernels of csrc/wdgcn.hip (widths up to
+8 x 8) and csrc/wdgcn_wide.hip (up to 64 x 64).
 
     WD_GCN       wgf:21-98    relu(AX·W), an LSTM over the T slices (sigmoid candidate), the edge head
     WD_GCN_reg   wgf:100-170  the same embedding with a per-node linear regression head (the SEIR script)
@@ -14,8 +15,9 @@ Contract kept from the reference
     never runs there and every call returns the training window's output (wgf:131-138).
   * The recurrence is causal: WD_GCN runs it only up to the last slice its edges read (``early_stop``), the logits are
     the same bits.  This spares the validation calls of the chess scripts 70 of 80 steps over zero-padded slices.
-  * Widths beyond the kernels' (H > 8 or F0 > 8) run the reference's statements as torch operators on the device
-    (ops.wdgcn_lstm_torch).  There is no CPU path.  ``group=`` (slice sharding) does not apply — the recurrence couples
+  * ops.wdgcn_lstm_route(F0, H) names the implementation: the lane-group kernels up to 8 x 8, the MFMA kernels up to
+    64 x 64 (the paper's hidden sizes 32 and 64), and only beyond that (H > 64 or F0 > 64) the reference's statements as
+    torch operators on the device (ops.wdgcn_lstm_torch).  There is no CPU path.  ``group=`` (slice sharding) does not apply — the recurrence couples
     all slices — and parameters are fp32 only: both raise.
 """
 from __future__ import annotations

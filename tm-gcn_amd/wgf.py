@@ -3,8 +3,8 @@
     import tmgcn_amd.wgf as wgf          # instead of: import wd_gcn_functions as wgf
 
 is the only edit a reference WD-GCN script needs (experiment_*_wd-gcn*.py, graph_SEIR_wd_gcn.py).  ``WD_GCN`` and
-``WD_GCN_reg`` are the classes of tmgcn_amd.wdgcn (the LSTM runs in csrc/wdgcn.hip) with ``host_operands`` set, as in
-tmgcn_amd.ehf: their outputs stay on the MI355X as ``hosted.DeviceResult`` and pull the host tensors a script combines
+``WD_GCN_reg`` are the classes of tmgcn_amd.wdgcn (the LSTM runs in csrc/wdgcn.hip, at widths beyond 8 up to 64 in
+csrc/wdgcn_wide.hip) with ``host_operands`` set, as in tmgcn_amd.ehf: their outputs stay on the MI355X as ``hosted.DeviceResult`` and pull the host tensors a script combines
 them with (targets, class weights, the criterion's arithmetic, ``argmax``) over to the device.
 """
 from . import wdgcn as _wdgcn
