@@ -45,7 +45,8 @@ typedef enum {
 enum { TMGCN_ACT_NONE = 0, TMGCN_ACT_RELU = 1, TMGCN_ACT_LEAKY = 2, TMGCN_ACT_SELU = 3 };
 
 /* Additions to ABI version 5 (backward compatible, the version stays 5): the WD-GCN entry points tmgcn_wdgcn_*, their
- * wide counterparts tmgcn_wdgcn_wide_* (widths up to 64) and the EvolveGCN-H entry points tmgcn_egcn_* (below).
+ * wide counterparts tmgcn_wdgcn_wide_* (widths up to 64) and the EvolveGCN-H entry points tmgcn_egcn_* and
+ * tmgcn_egcn_wide_* (below).
  * ABI version 5 = version 4 + tmgcn_pool_stats + the row_blocks partition argument of tmgcn_layer12_fwd/bwd_f32, the backward's AX / dW2 pair and tmgcn_layer12_bwd_forms_dw2 + tmgcn_head_loss_combine_f32 / tmgcn_head_loss_lanes (split rows of the one-pass head + loss plan) + the giant-row
  *   plan entry points tmgcn_spmm_csr_batched_f32_plan / tmgcn_spmm_gemm_f32_plan / tmgcn_spmm_giant_workspace_bytes; the launchers' scratch words (tile counters, hand-off blocks) are kept apart
  *   per stream (eager launches) and per recorded launch (hipGraph capture), and a launcher that cannot keep two launches
@@ -572,6 +573,32 @@ int tmgcn_egcn_bwd(const double* P, const double* X_g, const int32_t* idx, const
                    const double* W_seq, const double* gates, const float* dW32, const double* dWseq, double* dP,
                    double* dW0, float* dH, int64_t N, int32_t T_run, int32_t F, int32_t k, void* workspace,
                    int64_t workspace_bytes, void* stream);
+
+/* ---- EvolveGCN-H at widths up to 64 (additions to ABI 5) -------------------------------------------------------
+ * The same statements, tensors, packed P (F + 3·(2·F·F + F·k) values), tie rule and precision (fp64 wherever the entry
+ * points above have it) for the widths those reject: tmgcn_egcn_wide_supported(F, k): 1 <= F <= 64, 1 <= k <= 64 and not
+ * tmgcn_egcn_supported(F, k), so every pair of widths has exactly one kernel family.  tmgcn_egcn_supported and
+ * tmgcn_egcn_param_count keep their domain.  The arguments of tmgcn_egcn_wide_fwd / _bwd are those of tmgcn_egcn_fwd /
+ * _bwd, layer 2's fp64 rows (any F_prev >= 1) included.
+ * Forward, five launches whatever T_run is: per-block top 64 of every slice, their merge, the selected rows, the products
+ *   W_g·X_t of all steps, and the chain — the GRU is separable by column, one wave per column of W walks t with U_Z, U_R,
+ *   U_H in LDS.  Backward, five launches (and one memset when dH is asked for): the BPTT chain per column, dX of all
+ *   steps, the summary's dy and dH rows, the six F x F parameter gradients, and the biases and dp.  No atomics: every sum
+ *   has a fixed order, the same bits on every run; the summation orders differ from the narrow kernels'.
+ * The size functions return -1 for unsupported widths or negative sizes.  Arguments are validated before any device work
+ * (TMGCN_ERR_INVALID / TMGCN_ERR_WORKSPACE and a tmgcn_last_error() message); no host synchronisation and no allocation
+ * (capturable). */
+int tmgcn_egcn_wide_supported(int32_t F, int32_t k);
+int64_t tmgcn_egcn_wide_fwd_workspace_bytes(int64_t N, int32_t T_run, int32_t F, int32_t k);
+int tmgcn_egcn_wide_fwd(const float* H, const double* P, const double* W0, const int64_t* rowptr, const int32_t* col,
+                        const float* val, const float* X_prev, const double* W_prev, int32_t F_prev, int32_t* idx,
+                        double* y_sel, double* H_sel, double* X_g, double* W_seq, float* W32, double* gates, int64_t N,
+                        int32_t T_run, int32_t F, int32_t k, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t tmgcn_egcn_wide_bwd_workspace_bytes(int32_t T_run, int32_t F, int32_t k);
+int tmgcn_egcn_wide_bwd(const double* P, const double* X_g, const int32_t* idx, const double* y_sel, const double* H_sel,
+                        const double* W_seq, const double* gates, const float* dW32, const double* dWseq, double* dP,
+                        double* dW0, float* dH, int64_t N, int32_t T_run, int32_t F, int32_t k, void* workspace,
+                        int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,13 @@ SIGNATURES = {
                                  _p, _i64, _p]),
     "tmgcn_egcn_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "tmgcn_egcn_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _i64, _p]),
+    "tmgcn_egcn_wide_supported": (C.c_int, [_i32, _i32]),
+    "tmgcn_egcn_wide_fwd_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "tmgcn_egcn_wide_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32,
+                                      _i32, _p, _i64, _p]),
+    "tmgcn_egcn_wide_bwd_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "tmgcn_egcn_wide_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _i64,
+                                      _p]),
 }
 
 _lib = None

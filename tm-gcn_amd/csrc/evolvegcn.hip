@@ -27,6 +27,7 @@
 // with the fp64 rows H_sel the forward kept (it reads no H).
 // No atomics: the indices of one slice are distinct and every sum has a fixed order, two runs give the same bits.
 #include "common.h"
+#include "egcn_layout.h"   // eg_params, EgOff, eg_better, eg_norm, eg_sigmoid
 
 #include <math.h>
 
@@ -40,22 +41,7 @@ constexpr int kEgNodesPerThread = 8;
 constexpr int kEgNodesPerBlock = kEgThreads * kEgNodesPerThread;
 constexpr int kEgPF = 4;             // chain steps whose inputs are in flight ahead of the one being computed
 
-__host__ __device__ constexpr int64_t eg_params(int F, int k) { return F + 3LL * (2LL * F * F + (int64_t)F * k); }
 inline int64_t eg_blocks(int64_t N) { return (N + kEgNodesPerBlock - 1) / kEgNodesPerBlock; }
-
-// packed P (the reference's draw order, ef:37-46): p [F] | W_Z U_Z [F][F] B_Z [F][k] | W_R U_R B_R | W_H U_H B_H
-struct EgOff {
-  int W[3], U[3], B[3];
-  __host__ __device__ EgOff(int F, int k) {
-    for (int g = 0; g < 3; ++g) {
-      W[g] = F + g * (2 * F * F + F * k);
-      U[g] = W[g] + F * F;
-      B[g] = U[g] + F * F;
-    }
-  }
-};
-
-__device__ __forceinline__ bool eg_better(double s, int i, double s2, int i2) { return s > s2 || (s == s2 && i < i2); }
 
 // insert (cs, ci) into the descending list (s, ix): a fixed chain of compare-exchanges, static register indices only
 __device__ __forceinline__ void eg_insert(double (&s)[kEgL], int (&ix)[kEgL], double cs, int ci) {
@@ -151,12 +137,6 @@ __device__ __forceinline__ void eg_block_merge(double (&s)[kEgL], int (&ix)[kEgL
     }
     __syncthreads();
   }
-}
-
-__device__ __forceinline__ double eg_norm(const double* __restrict__ p, int F) {
-  double s = 0.0;
-  for (int f = 0; f < F; ++f) s = fma(p[f], p[f], s);
-  return sqrt(s);
 }
 
 // grid (blocks per slice, T_run): the best kEgL of the block's nodes -> cs / ci [T_run][nblk][kEgL]
@@ -270,8 +250,6 @@ __global__ __launch_bounds__(kEgThreads) void egcn_select_kernel(
       }
   }
 }
-
-__device__ __forceinline__ double eg_sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
 
 // one wave: W_seq[0] = W0, W_seq[t+1] = g(X_g[t], W_seq[t]) (ef:86-91); W32[t] = (float)W_seq[t+1]; gates (when
 // not null) keep Z, R, Ĥ of every step for the backward

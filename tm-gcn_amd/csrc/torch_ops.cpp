@@ -16,9 +16,10 @@
 //     tmgcn::wdgcn_fwd/bwd       tmgcn_wdgcn_*_f32                 wd_gcn_functions.py:70, 86-98 (WD-GCN)
 //     tmgcn::wdgcn_wide_fwd/bwd  tmgcn_wdgcn_wide_*_f32            the same at widths up to 64 (MFMA kernels)
 //     tmgcn::egcn_fwd/bwd        tmgcn_egcn_fwd / _bwd             evolvegcn_functions.py:80-95 (EvolveGCN-H)
+//     tmgcn::egcn_wide_fwd/bwd   tmgcn_egcn_wide_fwd / _bwd        the same at widths up to 64
 //   differentiable ops (registered under the Autograd key)
 //     tmgcn::m_transform, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm,
-//     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce, tmgcn::wdgcn_lstm, tmgcn::egcn_evolve
+//     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce, tmgcn::wdgcn_lstm, tmgcn::egcn_evolve, tmgcn::egcn_evolve_wide
 //
 // No kernels live here: every launch goes through the C-ABI shared library (libtmgcn_hip.so),
 // on torch's current HIP stream.  Errors surface as RuntimeError (TORCH_CHECK), the reference's
@@ -741,20 +742,27 @@ Tensor wdgcn_wide_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const
 }
 
 // ---- EvolveGCN-H (evolvegcn_functions.py:80-95): top-k summary + matrix-GRU weight evolution, and its backward ------
+// `wide` selects the kernels of csrc/evolvegcn_wide.hip (widths up to 64): the same tensors through tmgcn_egcn_wide_*
 bool egcn_supported(int64_t F, int64_t k) { return tmgcn_egcn_supported((int32_t)F, (int32_t)k) != 0; }
+bool egcn_wide_supported(int64_t F, int64_t k) { return tmgcn_egcn_wide_supported((int32_t)F, (int32_t)k) != 0; }
 
-static void egcn_check(const Tensor& H, const Tensor& P, const Tensor& W0, int64_t k, int64_t T_run) {
+static void egcn_check(const Tensor& H, const Tensor& P, const Tensor& W0, int64_t k, int64_t T_run, bool wide = false) {
   want(H, "egcn H");
   want(P, "egcn P", at::kDouble);
   want(W0, "egcn W_init", at::kDouble);
   TORCH_CHECK(H.dim() == 3, "egcn: H must be [T, N, F], got ", H.sizes());
   const int64_t F = H.size(2), N = H.size(1);
-  TORCH_CHECK(tmgcn_egcn_supported((int32_t)F, (int32_t)k), "egcn: F=", F, ", k=", k,
-              " outside the kernel's widths (1..8 each)");
+  if (wide) {
+    TORCH_CHECK(tmgcn_egcn_wide_supported((int32_t)F, (int32_t)k), "egcn_wide: F=", F, ", k=", k,
+                " outside the wide kernels' widths (1..64 each, not both <= 8)");
+  } else {
+    TORCH_CHECK(tmgcn_egcn_supported((int32_t)F, (int32_t)k), "egcn: F=", F, ", k=", k,
+                " outside the kernel's widths (1..8 each)");
+  }
   TORCH_CHECK(T_run >= 0 && T_run <= H.size(0), "egcn: T_run=", T_run, " outside 0..", H.size(0));
   TORCH_CHECK(T_run == 0 || N >= k, "egcn: topk needs N >= k (N=", N, ", k=", k, ")");
-  TORCH_CHECK(P.numel() == tmgcn_egcn_param_count((int32_t)F, (int32_t)k), "egcn: P holds ", P.numel(),
-              " values, the packed parameters of F=", F, ", k=", k, " are ", tmgcn_egcn_param_count((int32_t)F, (int32_t)k));
+  const int64_t np = F + 3 * (2 * F * F + F * k);              // = tmgcn_egcn_param_count on its domain
+  TORCH_CHECK(P.numel() == np, "egcn: P holds ", P.numel(), " values, the packed parameters of F=", F, ", k=", k, " are ", np);
   TORCH_CHECK(W0.numel() == F * k, "egcn: W_init must be [F=", F, ", k=", k, "], got ", W0.sizes());
   TORCH_CHECK(H.device() == P.device() && H.device() == W0.device(), "egcn: H, P and W_init must be on one device");
 }
@@ -798,10 +806,10 @@ static EgcnRows egcn_rows(const Tensor& H, int64_t T_run, const OptTensor& rowpt
 
 // (W_seq [T_run+1,F,k] fp64, W32 [T_run,F,k], idx [T_run,k] int32, y_sel [T_run,k], H_sel [T_run,k,F], X_g [T_run,F,k],
 //  gates [T_run,3,F,k])
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egcn_fwd(
-    const Tensor& H, const Tensor& P, const Tensor& W0, int64_t k, int64_t T_run, bool need_gates, const OptTensor& rowptr,
-    const OptTensor& col, const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
-  egcn_check(H, P, W0, k, T_run);
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egcn_fwd_any(
+    bool wide, const Tensor& H, const Tensor& P, const Tensor& W0, int64_t k, int64_t T_run, bool need_gates,
+    const OptTensor& rowptr, const OptTensor& col, const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
+  egcn_check(H, P, W0, k, T_run, wide);
   const EgcnRows rows = egcn_rows(H, T_run, rowptr, col, val, X_prev, W_prev);
   c10::DeviceGuard g(H.device());
   const int64_t N = H.size(1), F = H.size(2);
@@ -810,23 +818,34 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egcn_fwd(
   Tensor idx = at::empty({T_run, k}, H.options().dtype(at::kInt)), ysel = at::empty({T_run, k}, f64);
   Tensor Hsel = at::empty({T_run, k, F}, f64), Xg = at::empty({T_run, F, k}, f64);
   Tensor gates = need_gates ? at::empty({T_run, 3, F, k}, f64) : none_like(P);
-  const int64_t need = tmgcn_egcn_fwd_workspace_bytes(N, (int32_t)T_run, (int32_t)F, (int32_t)k);
+  const int64_t need = (wide ? tmgcn_egcn_wide_fwd_workspace_bytes : tmgcn_egcn_fwd_workspace_bytes)(N, (int32_t)T_run, (int32_t)F,
+                                                                                                      (int32_t)k);
   Tensor ws = at::empty({need > 0 ? need : 1}, H.options().dtype(at::kByte));
-  ok(tmgcn_egcn_fwd((const float*)ptr(H), (const double*)ptr(P), (const double*)ptr(W0), rows.rowptr, rows.col, rows.val,
+  ok((wide ? tmgcn_egcn_wide_fwd : tmgcn_egcn_fwd)((const float*)ptr(H), (const double*)ptr(P), (const double*)ptr(W0), rows.rowptr, rows.col, rows.val,
                     rows.X, rows.W, rows.F_prev, (int32_t*)ptr(idx), (double*)ptr(ysel), (double*)ptr(Hsel),
                     (double*)ptr(Xg), (double*)ptr(Wseq), (float*)ptr(W32), need_gates ? (double*)ptr(gates) : nullptr, N,
                     (int32_t)T_run, (int32_t)F, (int32_t)k, ptr(ws), ws.numel(), stream_of(H)),
-     "tmgcn_egcn_fwd");
+     wide ? "tmgcn_egcn_wide_fwd" : "tmgcn_egcn_fwd");
   return {Wseq, W32, idx, ysel, Hsel, Xg, gates};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egcn_fwd(
+    const Tensor& H, const Tensor& P, const Tensor& W0, int64_t k, int64_t T_run, bool need_gates, const OptTensor& rowptr,
+    const OptTensor& col, const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
+  return egcn_fwd_any(false, H, P, W0, k, T_run, need_gates, rowptr, col, val, X_prev, W_prev);
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> egcn_wide_fwd(
+    const Tensor& H, const Tensor& P, const Tensor& W0, int64_t k, int64_t T_run, bool need_gates, const OptTensor& rowptr,
+    const OptTensor& col, const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
+  return egcn_fwd_any(true, H, P, W0, k, T_run, need_gates, rowptr, col, val, X_prev, W_prev);
 }
 
 // (dP, dW0, dH) from the gradients of W_seq (fp64, may be undefined) and of W32 (fp32, may be undefined)
-std::tuple<Tensor, Tensor, Tensor> egcn_bwd(const Tensor& H, const Tensor& P, const Tensor& W0, const Tensor& Xg,
-                                            const Tensor& idx, const Tensor& ysel, const Tensor& Hsel, const Tensor& Wseq,
-                                            const Tensor& gates, const OptTensor& dWseq_, const OptTensor& dW32_,
-                                            bool need_dH) {
+static std::tuple<Tensor, Tensor, Tensor> egcn_bwd_any(bool wide, const Tensor& H, const Tensor& P, const Tensor& W0,
+                                                       const Tensor& Xg, const Tensor& idx, const Tensor& ysel,
+                                                       const Tensor& Hsel, const Tensor& Wseq, const Tensor& gates,
+                                                       const OptTensor& dWseq_, const OptTensor& dW32_, bool need_dH) {
   const int64_t T_run = Wseq.dim() == 3 ? Wseq.size(0) - 1 : -1, k = Wseq.dim() == 3 ? Wseq.size(2) : -1;
-  egcn_check(H, P, W0, k, T_run);
+  egcn_check(H, P, W0, k, T_run, wide);
   const int64_t N = H.size(1), F = H.size(2);
   want(Wseq, "egcn W_seq", at::kDouble);
   TORCH_CHECK(Wseq.size(1) == F, "egcn_bwd: W_seq ", Wseq.sizes(), " does not match F=", F);
@@ -855,16 +874,29 @@ std::tuple<Tensor, Tensor, Tensor> egcn_bwd(const Tensor& H, const Tensor& P, co
   Tensor dP = at::empty({P.numel()}, P.options()), dW0 = at::empty({F, k}, P.options());
   Tensor dH = need_dH ? (H.size(0) == T_run ? at::empty(H.sizes(), H.options()) : at::zeros(H.sizes(), H.options()))
                       : Tensor();
-  const int64_t need = tmgcn_egcn_bwd_workspace_bytes((int32_t)T_run, (int32_t)F, (int32_t)k);
+  const int64_t need = (wide ? tmgcn_egcn_wide_bwd_workspace_bytes : tmgcn_egcn_bwd_workspace_bytes)((int32_t)T_run, (int32_t)F,
+                                                                                                      (int32_t)k);
   Tensor ws = at::empty({need > 0 ? need : 1}, H.options().dtype(at::kByte));
-  ok(tmgcn_egcn_bwd((const double*)ptr(P), (const double*)ptr(Xg), (const int32_t*)ptr(idx), (const double*)ptr(ysel),
+  ok((wide ? tmgcn_egcn_wide_bwd : tmgcn_egcn_bwd)((const double*)ptr(P), (const double*)ptr(Xg), (const int32_t*)ptr(idx), (const double*)ptr(ysel),
                     (const double*)ptr(Hsel), (const double*)ptr(Wseq), (const double*)ptr(gates),
                     dW32.defined() ? (const float*)ptr(dW32) : nullptr,
                     dWseq.defined() ? (const double*)ptr(dWseq) : nullptr, (double*)ptr(dP), (double*)ptr(dW0),
                     need_dH ? (float*)ptr(dH) : nullptr, N, (int32_t)T_run, (int32_t)F, (int32_t)k, ptr(ws), ws.numel(),
                     stream_of(H)),
-     "tmgcn_egcn_bwd");
+     wide ? "tmgcn_egcn_wide_bwd" : "tmgcn_egcn_bwd");
   return {dP, dW0.view(W0.sizes()), dH};
+}
+std::tuple<Tensor, Tensor, Tensor> egcn_bwd(const Tensor& H, const Tensor& P, const Tensor& W0, const Tensor& Xg,
+                                            const Tensor& idx, const Tensor& ysel, const Tensor& Hsel, const Tensor& Wseq,
+                                            const Tensor& gates, const OptTensor& dWseq_, const OptTensor& dW32_,
+                                            bool need_dH) {
+  return egcn_bwd_any(false, H, P, W0, Xg, idx, ysel, Hsel, Wseq, gates, dWseq_, dW32_, need_dH);
+}
+std::tuple<Tensor, Tensor, Tensor> egcn_wide_bwd(const Tensor& H, const Tensor& P, const Tensor& W0, const Tensor& Xg,
+                                                 const Tensor& idx, const Tensor& ysel, const Tensor& Hsel,
+                                                 const Tensor& Wseq, const Tensor& gates, const OptTensor& dWseq_,
+                                                 const OptTensor& dW32_, bool need_dH) {
+  return egcn_bwd_any(true, H, P, W0, Xg, idx, ysel, Hsel, Wseq, gates, dWseq_, dW32_, need_dH);
 }
 
 bool edge_head_supported(int64_t F, int64_t C) { return tmgcn_edge_head_supported((int32_t)F, (int32_t)C) != 0; }
@@ -1257,18 +1289,20 @@ struct WdgcnWideLstmFn : public torch::autograd::Function<WdgcnWideLstmFn> {
 struct EgcnEvolveFn : public torch::autograd::Function<EgcnEvolveFn> {
   static variable_list forward(AutogradContext* ctx, const Tensor& H, const Tensor& p, at::TensorList gates,
                                const Tensor& W0, at::TensorList rows, int64_t k, int64_t T_run, bool need,
-                               bool need_dH) {
-    // rows: empty, or layer 2's (rowptr, col, val, X_prev, W_prev)
+                               bool need_dH, bool wide) {
+    // rows: empty, or layer 2's (rowptr, col, val, X_prev, W_prev); wide: the kernels of csrc/evolvegcn_wide.hip
     at::AutoDispatchBelowADInplaceOrView guard;
     std::vector<Tensor> parts{p.reshape({-1})};
     for (const Tensor& q : gates) parts.push_back(q.reshape({-1}));
     Tensor P = at::cat(parts).contiguous();
     Tensor W0c = W0.contiguous();
     auto opt = [&](size_t i) { return i < rows.size() ? OptTensor(rows[i]) : OptTensor(); };
-    auto [Wseq, W32, idx, ysel, Hsel, Xg, gt] = egcn_fwd(H, P, W0c, k, T_run, need, opt(0), opt(1), opt(2), opt(3), opt(4));
+    auto [Wseq, W32, idx, ysel, Hsel, Xg, gt] =
+        egcn_fwd_any(wide, H, P, W0c, k, T_run, need, opt(0), opt(1), opt(2), opt(3), opt(4));
     if (need) {
       ctx->save_for_backward({H, P, W0c, Xg, idx, ysel, Hsel, Wseq, gt});
       ctx->saved_data["need_dH"] = need_dH;
+      ctx->saved_data["wide"] = wide;
       ctx->saved_data["n_gates"] = (int64_t)gates.size();
       ctx->saved_data["n_rows"] = (int64_t)rows.size();
       ctx->saved_data["p_numel"] = p.numel();
@@ -1281,7 +1315,8 @@ struct EgcnEvolveFn : public torch::autograd::Function<EgcnEvolveFn> {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto sv = ctx->get_saved_variables();
     const bool need_dH = ctx->saved_data["need_dH"].toBool();
-    auto [dP, dW0, dH] = egcn_bwd(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7], sv[8], grads[0], grads[1], need_dH);
+    auto [dP, dW0, dH] = egcn_bwd_any(ctx->saved_data["wide"].toBool(), sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7],
+                                      sv[8], grads[0], grads[1], need_dH);
     const int64_t n_gates = ctx->saved_data["n_gates"].toInt();
     variable_list out;
     out.push_back(need_dH ? dH : Tensor());
@@ -1297,9 +1332,9 @@ struct EgcnEvolveFn : public torch::autograd::Function<EgcnEvolveFn> {
     for (int64_t i = 0; i < n_gates; ++i) out.push_back(take(ctx->saved_data["g" + std::to_string(i)].toIntVector()));
     out.push_back(dW0);
     // rows: the gradient of layer 2's fp64 rows reaches W_prev through dH and the GCONV that formed H; then k, T_run,
-    // need, need_dH
+    // need, need_dH, wide
     const int64_t n_rows = ctx->saved_data["n_rows"].toInt();
-    for (int64_t i = 0; i < n_rows + 4; ++i) out.push_back(Tensor());
+    for (int64_t i = 0; i < n_rows + 5; ++i) out.push_back(Tensor());
     return out;
   }
 };
@@ -1390,9 +1425,10 @@ Tensor wdgcn_lstm_wide_ad(const Tensor& AX, const Tensor& P, const Tensor& h0, c
               "wdgcn_lstm_wide: AX, h_init and c_init are constants (no gradient is formed for them)");
   return WdgcnWideLstmFn::apply(AX, P, h0, c0, H, T_run, grad && P.requires_grad());
 }
-std::tuple<Tensor, Tensor> egcn_evolve_ad(const Tensor& H, const Tensor& p, at::TensorList gates, const Tensor& W0,
-                                          int64_t k, int64_t T_run, const OptTensor& rowptr, const OptTensor& col,
-                                          const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
+static std::tuple<Tensor, Tensor> egcn_evolve_any(bool wide, const Tensor& H, const Tensor& p, at::TensorList gates,
+                                                  const Tensor& W0, int64_t k, int64_t T_run, const OptTensor& rowptr,
+                                                  const OptTensor& col, const OptTensor& val, const OptTensor& X_prev,
+                                                  const OptTensor& W_prev) {
   TORCH_CHECK(gates.size() == 9, "egcn_evolve: expected the nine gate matrices W_Z U_Z B_Z W_R U_R B_R W_H U_H B_H, got ",
               gates.size());
   const bool grad = at::GradMode::is_enabled();
@@ -1404,8 +1440,18 @@ std::tuple<Tensor, Tensor> egcn_evolve_ad(const Tensor& H, const Tensor& p, at::
                 "egcn_evolve: the fp64 rows of layer 2 need rowptr, col, val, X_prev and W_prev together");
     rows = {*rowptr, *col, *val, *X_prev, *W_prev};
   }
-  auto r = EgcnEvolveFn::apply(H, p, gates, W0, at::TensorList(rows), k, T_run, grad && any, grad && H.requires_grad());
+  auto r = EgcnEvolveFn::apply(H, p, gates, W0, at::TensorList(rows), k, T_run, grad && any, grad && H.requires_grad(), wide);
   return {r[0], r[1]};
+}
+std::tuple<Tensor, Tensor> egcn_evolve_ad(const Tensor& H, const Tensor& p, at::TensorList gates, const Tensor& W0,
+                                          int64_t k, int64_t T_run, const OptTensor& rowptr, const OptTensor& col,
+                                          const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
+  return egcn_evolve_any(false, H, p, gates, W0, k, T_run, rowptr, col, val, X_prev, W_prev);
+}
+std::tuple<Tensor, Tensor> egcn_evolve_wide_ad(const Tensor& H, const Tensor& p, at::TensorList gates, const Tensor& W0,
+                                               int64_t k, int64_t T_run, const OptTensor& rowptr, const OptTensor& col,
+                                               const OptTensor& val, const OptTensor& X_prev, const OptTensor& W_prev) {
+  return egcn_evolve_any(true, H, p, gates, W0, k, T_run, rowptr, col, val, X_prev, W_prev);
 }
 Tensor weighted_ce_ad(const Tensor& logits, const Tensor& target, const Tensor& weight, int64_t ignore_index) {
   return WeightedCeFn::apply(logits, target, weight, ignore_index);
@@ -1484,6 +1530,13 @@ TORCH_LIBRARY(tmgcn, m) {
   m.def("egcn_bwd(Tensor H, Tensor P, Tensor W0, Tensor X_g, Tensor idx, Tensor y_sel, Tensor H_sel, Tensor W_seq, "
         "Tensor gates, Tensor? dW_seq, Tensor? dW32, bool need_dH) -> (Tensor, Tensor, Tensor)");
   m.def("egcn_supported(int F, int k) -> bool", &egcn_supported);
+  m.def("egcn_wide_fwd(Tensor H, Tensor P, Tensor W0, int k, int T_run, bool need_gates, Tensor? rowptr=None, Tensor? col=None, "
+        "Tensor? val=None, Tensor? X_prev=None, Tensor? W_prev=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("egcn_wide_bwd(Tensor H, Tensor P, Tensor W0, Tensor X_g, Tensor idx, Tensor y_sel, Tensor H_sel, Tensor W_seq, "
+        "Tensor gates, Tensor? dW_seq, Tensor? dW32, bool need_dH) -> (Tensor, Tensor, Tensor)");
+  m.def("egcn_wide_supported(int F, int k) -> bool", &egcn_wide_supported);
+  m.def("egcn_evolve_wide(Tensor H, Tensor p, Tensor[] gate_params, Tensor W_init, int k, int T_run, Tensor? rowptr=None, "
+        "Tensor? col=None, Tensor? val=None, Tensor? X_prev=None, Tensor? W_prev=None) -> (Tensor, Tensor)");
   m.def("egcn_evolve(Tensor H, Tensor p, Tensor[] gate_params, Tensor W_init, int k, int T_run, Tensor? rowptr=None, "
         "Tensor? col=None, Tensor? val=None, Tensor? X_prev=None, Tensor? W_prev=None) -> (Tensor, Tensor)");
 }
@@ -1515,6 +1568,8 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("wdgcn_wide_bwd", &wdgcn_wide_bwd);
   m.impl("egcn_fwd", &egcn_fwd);
   m.impl("egcn_bwd", &egcn_bwd);
+  m.impl("egcn_wide_fwd", &egcn_wide_fwd);
+  m.impl("egcn_wide_bwd", &egcn_wide_bwd);
   // below the Autograd key (inference mode, or called from inside another autograd node) the
   // differentiable operators are their plain forwards
   m.impl("m_transform", &m_transform_ad);
@@ -1530,6 +1585,7 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
   m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
   m.impl("egcn_evolve", &egcn_evolve_ad);
+  m.impl("egcn_evolve_wide", &egcn_evolve_wide_ad);
 }
 
 TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
@@ -1546,6 +1602,7 @@ TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
   m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
   m.impl("egcn_evolve", &egcn_evolve_ad);
+  m.impl("egcn_evolve_wide", &egcn_evolve_wide_ad);
 }
 
 // a CPU tensor reaching a kernel-level op gets the reference-style RuntimeError, not "no kernel"
@@ -1571,4 +1628,5 @@ TORCH_LIBRARY_IMPL(tmgcn, CPU, m) {
   m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
   m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
   m.impl("egcn_evolve", &egcn_evolve_ad);
+  m.impl("egcn_evolve_wide", &egcn_evolve_wide_ad);
 }

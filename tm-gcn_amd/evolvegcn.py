@@ -1,6 +1,6 @@
 """Drop-in EvolveGCN-H modules (TensorGCN-master/evolvegcn_functions.py, "ef"): the fourth model family the reference's
 drivers compare (experiment_*_evolvegcn*.py, graph_SEIR_evolvegcn.py), the weight evolution computed by the HIP kernels
-of csrc/evolvegcn.hip and the GCONVs by the batched per-slice GEMM / SpMM+GEMM of the other layers.
+of csrc/evolvegcn.hip / csrc/evolvegcn_wide.hip and the GCONVs by the batched per-slice GEMM / SpMM+GEMM of the other layers.
 
     EvolveGCN_1_layer  ef:22-101   W_t = GRU(summary(X_t), W_{t-1}), Y_t = (A_t·X_t)·W_t, the edge head
     EvolveGCN_2_layer  ef:104-213  two such layers, ReLU after the first
@@ -23,8 +23,9 @@ Contract kept from the reference
   * Scores, summary and GRU are fp64 (the reference's precision); the GCONVs and the head fp32.  Layer 2 ranks the
     fp32 H1 its GCONV uses and forms the k selected rows again in fp64 from Â, X and the fp64 W_t of layer 1.  Equal
     scores select the lower node index (include/tmgcn.h).
-  * Widths beyond the kernels' (F or k > 8) run the reference's statements as torch operators on the device
-    (ops.egcn_evolve_torch).  There is no CPU path.  ``group=`` (slice sharding) does not apply — the GRU couples all
+  * ops.egcn_evolve_route(F, k) names the implementation of a layer's evolution: csrc/evolvegcn.hip up to 8 x 8,
+    csrc/evolvegcn_wide.hip up to 64 x 64; widths beyond (F or k > 64) run the reference's statements as torch
+    operators on the device (ops.egcn_evolve_torch).  There is no CPU path.  ``group=`` (slice sharding) does not apply — the GRU couples all
     slices — and ``param_dtype`` other than the reference's: both raise.
   * Train with ``torch.optim.SGD`` as the drivers do (it takes the fp64 / fp32 mix).  tmgcn_amd.optim.FusedSGD and
     layers.fused_train_step do not apply to these models (FusedSGD refuses fp64 parameters); graphs.GraphedTrainStep

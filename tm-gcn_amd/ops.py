@@ -786,9 +786,31 @@ def egcn_supported(F: int, k: int) -> bool:
     return kernels.name == "hip" and _egcn_widths_ok(int(F), int(k))
 
 
+@functools.lru_cache(maxsize=None)
+def _egcn_wide_widths_ok(F: int, k: int) -> bool:
+    return bool(_lib.load().tmgcn_egcn_wide_supported(F, k))
+
+
+def egcn_wide_supported(F: int, k: int) -> bool:
+    """True when the wide EvolveGCN-H kernels (csrc/evolvegcn_wide.hip, fp64) cover the widths: 1 <= F <= 64,
+    1 <= k <= 64 and not both <= 8 (those belong to the narrow kernels)."""
+    return kernels.name == "hip" and _egcn_wide_widths_ok(int(F), int(k))
+
+
+def egcn_evolve_route(F: int, k: int) -> str:
+    """Which implementation ops.egcn_evolve runs at these widths: "narrow" (csrc/evolvegcn.hip), "wide"
+    (csrc/evolvegcn_wide.hip) or "torch" (egcn_evolve_torch: widths beyond 64)."""
+    if egcn_supported(F, k):
+        return "narrow"
+    if egcn_wide_supported(F, k):
+        return "wide"
+    return "torch"
+
+
 def egcn_evolve_torch(H: torch.Tensor, p: torch.Tensor, gates, W_init: torch.Tensor, T_run: Optional[int] = None):
     """The weight evolution of ef:80-95 as torch operators on the tensors' device: the path of widths the kernels do not
-    cover, and the naive port they are measured against (tools/evolvegcn_epoch.py).  Returns (W_seq, W32) like
+    cover (beyond 64), and the naive port they are measured against (tools/evolvegcn_epoch.py,
+    tools/evolvegcn_wide_epoch.py).  Returns (W_seq, W32) like
     egcn_evolve; torch.topk's order of equal scores is its own."""
     wz, uz, bz, wr, ur, br, wh, uh, bh = gates
     T_run = H.shape[0] if T_run is None else int(T_run)
@@ -816,9 +838,11 @@ def egcn_evolve(H: torch.Tensor, p: torch.Tensor, gates, W_init: torch.Tensor, T
     GCONV).  ``gates``: the nine matrices in the reference's order (EGCN_GATE_NAMES); p, the gates and W_init fp64.
     ``rows`` = (A, X_prev, W_prev_seq) for layer 2, whose H = relu(Â_t·X_prev_t·W_prev_t) is fp32: the selected rows
     are formed again in fp64 from them (include/tmgcn.h), the ranking stays that of H.
-    Three forward launches (summary, merge, chain) and two backward launches (chain BPTT, parameter sums + the summary's
-    backward) when egcn_supported(F, k), else the reference's statements as torch operators on the device.  Gradients
-    for p, the gates, W_init, and H when H requires one (layer 2)."""
+    Dispatched by egcn_evolve_route(F, k): three forward launches (summary, merge, chain) and two backward launches
+    (chain BPTT, parameter sums + the summary's backward) of the narrow kernels up to 8 x 8; five forward and five
+    backward launches of the wide kernels (csrc/evolvegcn_wide.hip: the chain split by column of W, the input-side
+    products and the parameter sums off the chain) up to 64 x 64; beyond that the reference's statements as torch
+    operators on the device.  Gradients for p, the gates, W_init, and H when H requires one (layer 2)."""
     gates = list(gates)
     if len(gates) != 9:
         raise RuntimeError(f"egcn_evolve: expected the nine gate matrices {EGCN_GATE_NAMES}, got {len(gates)}")
@@ -828,10 +852,12 @@ def egcn_evolve(H: torch.Tensor, p: torch.Tensor, gates, W_init: torch.Tensor, T
         raise RuntimeError(f"egcn_evolve: T_run={T_run} outside 0..{H.shape[0]}")
     if T_run and H.shape[1] < k:
         raise RuntimeError(f"egcn_evolve: topk needs N >= k (N={H.shape[1]}, k={k}) (ef:82)")
-    if not egcn_supported(F, k):
+    route = egcn_evolve_route(F, k)
+    if route == "torch":
         return egcn_evolve_torch(H, p, gates, W_init, T_run)
+    op = kernels.ops.egcn_evolve if route == "narrow" else kernels.ops.egcn_evolve_wide
     if rows is not None:
         A, Xp, Wp = rows
-        return kernels.ops.egcn_evolve(_want(H, "egcn_evolve H"), p, gates, W_init, k, T_run, A.rowptr, A.col, A.val,
-                                       _want(Xp, "egcn_evolve X_prev"), Wp)
-    return kernels.ops.egcn_evolve(_want(H, "egcn_evolve H"), p, gates, W_init, k, T_run)
+        return op(_want(H, "egcn_evolve H"), p, gates, W_init, k, T_run, A.rowptr, A.col, A.val,
+                  _want(Xp, "egcn_evolve X_prev"), Wp)
+    return op(_want(H, "egcn_evolve H"), p, gates, W_init, k, T_run)
