@@ -139,6 +139,45 @@ inline int persistent_grid_reserved(K kernel, int block_threads, int reserve, si
   return g < 64 ? 64 : g;
 }
 
+// The caller's workspace against what the entry point `who` needs.
+inline int check_workspace(const char* who, const void* workspace, int64_t bytes, int64_t need) {
+  if (workspace && bytes >= need) return TMGCN_OK;
+  set_error("%s: workspace of %lld bytes, %lld needed", who, (long long)bytes, (long long)need);
+  return TMGCN_ERR_WORKSPACE;
+}
+
+// A block may use more than 64 KB of LDS only after the kernel has been told so.  The runtime is asked once per kernel,
+// device and host thread, and again only for more bytes than that thread was granted: a table keyed like
+// persistent_grid's.  A full table overwrites its oldest entry, and that kernel is simply asked for again.  Like there, K
+// is the function-pointer type, so each argument list in each translation unit has a table of its own: the ten kernels
+// that call this today spread over four tables of at most four kernels.
+template <typename K>
+inline int allow_large_lds(K kernel, size_t bytes, const char* what) {
+  if (bytes <= 64 * 1024) return TMGCN_OK;
+  struct Entry { const void* k; int dev; size_t bytes; };
+  constexpr int kSlots = 32;
+  thread_local Entry table[kSlots] = {};
+  thread_local int next = 0;
+  const void* key = reinterpret_cast<const void*>(kernel);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  Entry* e = nullptr;
+  for (int i = 0; i < kSlots && !e; ++i)
+    if (table[i].k == key && table[i].dev == dev) e = &table[i];
+  if (e && e->bytes >= bytes) return TMGCN_OK;
+  if (hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: %zu bytes of LDS per block refused", what, bytes);
+    return TMGCN_ERR_LAUNCH;
+  }
+  if (!e) {
+    e = &table[next];
+    next = (next + 1) % kSlots;
+  }
+  *e = Entry{key, dev, bytes};
+  return TMGCN_OK;
+}
+
 // 4x4 transpose across a lane quad: on entry register k of lane j (j = lane & 3) holds M[k][j], on
 // exit it holds M[j][k].  The MFMA accumulator layout has the output COLUMN on the lane and four
 // consecutive ROWS in consecutive registers, so a plain epilogue stores one dword per lane per row

@@ -27,7 +27,7 @@
 // with the fp64 rows H_sel the forward kept (it reads no H).
 // No atomics: the indices of one slice are distinct and every sum has a fixed order, two runs give the same bits.
 #include "common.h"
-#include "egcn_layout.h"   // eg_params, EgOff, eg_better, eg_norm, eg_sigmoid
+#include "egcn_layout.h"   // eg_params, EgOff, eg_better, eg_norm, eg_sigmoid; eg_check, eg_check_rows, eg_bwd_prepare
 
 #include <math.h>
 
@@ -512,33 +512,19 @@ extern "C" int64_t tmgcn_egcn_bwd_workspace_bytes(int32_t T_run, int32_t F, int3
   return (int64_t)T_run * 4LL * F * k * (int64_t)sizeof(double);
 }
 
-static int eg_check(const char* who, int64_t N, int32_t T_run, int32_t F, int32_t k) {
-  TMGCN_REQUIRE(tmgcn_egcn_supported(F, k), "%s: F=%d, k=%d outside 1..%d x 1..%d", who, F, k, kEgMax, kEgMax);
-  TMGCN_REQUIRE(T_run >= 0 && T_run <= 65535, "%s: T_run=%d outside 0..65535", who, T_run);
-  TMGCN_REQUIRE(N >= 0 && N < (int64_t)0x7fffffff, "%s: N=%lld outside 0..2^31-2", who, (long long)N);
-  TMGCN_REQUIRE(T_run == 0 || N >= k, "%s: top-k needs N >= k (N=%lld, k=%d) (ef:82)", who, (long long)N, k);
-  TMGCN_REQUIRE((int64_t)T_run * N * F < (int64_t)1 << 62, "%s: T_run x N x F too large", who);
-  return TMGCN_OK;
-}
-
 extern "C" int tmgcn_egcn_fwd(const float* H, const double* P, const double* W0, const int64_t* rowptr,
                               const int32_t* col, const float* val, const float* X_prev, const double* W_prev,
                               int32_t F_prev, int32_t* idx, double* ysel, double* Hsel, double* Xg, double* Wseq,
                               float* W32, double* gates, int64_t N, int32_t T_run, int32_t F, int32_t k,
                               void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = eg_check("egcn_fwd", N, T_run, F, k)) return rc;
-  TMGCN_REQUIRE(P && W0 && Wseq, "egcn_fwd: null pointer");
-  TMGCN_REQUIRE(T_run == 0 || (H && idx && ysel && Hsel && Xg && W32), "egcn_fwd: null pointer");
-  TMGCN_REQUIRE(!rowptr || (X_prev && W_prev && F_prev >= 1),
-                "egcn_fwd: the fp64 rows of layer 2 need X_prev, W_prev and F_prev >= 1 (F_prev=%d)", F_prev);
-  TMGCN_REQUIRE(!rowptr || (int64_t)T_run * N * F_prev < (int64_t)1 << 62, "egcn_fwd: T_run x N x F_prev too large");
+  if (int rc = eg_check("egcn_fwd", tmgcn_egcn_supported(F, k), kEgMax, 0, N, T_run, F, k, P && W0 && Wseq,
+                        H && idx && ysel && Hsel && Xg && W32))
+    return rc;
+  if (int rc = eg_check_rows("egcn_fwd", rowptr, X_prev && W_prev, F_prev, N, T_run)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (T_run > 0) {
-    const int64_t need = tmgcn_egcn_fwd_workspace_bytes(N, T_run, F, k);
-    if (!workspace || workspace_bytes < need) {
-      set_error("egcn_fwd: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-      return TMGCN_ERR_WORKSPACE;
-    }
+    if (int rc = check_workspace("egcn_fwd", workspace, workspace_bytes, tmgcn_egcn_fwd_workspace_bytes(N, T_run, F, k)))
+      return rc;
     const int64_t nblk = eg_blocks(N);
     TMGCN_REQUIRE(nblk < (int64_t)1 << 31, "egcn_fwd: N=%lld too large", (long long)N);
     double* cs = static_cast<double*>(workspace);
@@ -557,19 +543,13 @@ extern "C" int tmgcn_egcn_bwd(const double* P, const double* Xg, const int32_t* 
                               const double* Hsel, const double* Wseq, const double* gates, const float* dW32,
                               const double* dWseq, double* dP, double* dW0, float* dH, int64_t N, int32_t T_run,
                               int32_t F, int32_t k, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = eg_check("egcn_bwd", N, T_run, F, k)) return rc;
-  TMGCN_REQUIRE(P && Wseq && dP && dW0, "egcn_bwd: null pointer");
-  TMGCN_REQUIRE(T_run == 0 || (Xg && idx && ysel && Hsel && gates), "egcn_bwd: null pointer");
+  if (int rc = eg_check("egcn_bwd", tmgcn_egcn_supported(F, k), kEgMax, 0, N, T_run, F, k, P && Wseq && dP && dW0,
+                        Xg && idx && ysel && Hsel && gates))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t need = tmgcn_egcn_bwd_workspace_bytes(T_run, F, k);
-  if (T_run > 0 && (!workspace || workspace_bytes < need)) {
-    set_error("egcn_bwd: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-    return TMGCN_ERR_WORKSPACE;
-  }
-  if (dH && T_run > 0 && hipMemsetAsync(dH, 0, (size_t)T_run * N * F * sizeof(float), st) != hipSuccess) {
-    set_error("egcn_bwd: hipMemsetAsync failed");
-    return TMGCN_ERR_LAUNCH;
-  }
+  if (int rc = eg_bwd_prepare("egcn_bwd", workspace, workspace_bytes, tmgcn_egcn_bwd_workspace_bytes(T_run, F, k), dH, N,
+                              T_run, F, st))
+    return rc;
   double* dA = static_cast<double*>(workspace);
   hipLaunchKernelGGL(egcn_chain_bwd_kernel, dim3(1), dim3(64), 0, st, P, Wseq, gates, dW32, dWseq, (int)T_run, (int)F,
                      (int)k, dA, dW0);

@@ -540,25 +540,6 @@ __global__ __launch_bounds__(64) void egw_small_grad_kernel(const double* __rest
   dP[o.B[g] + r] = s;
 }
 
-// a block may use more than 64 KB of LDS only after the kernel has been told so: once per kernel, device and host thread
-template <typename K>
-int egw_allow_lds(K kernel, size_t bytes, int slot, const char* what) {
-  if (bytes <= 64 * 1024) return TMGCN_OK;
-  thread_local size_t allowed[16][2] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  const bool cache = dev >= 0 && dev < 16;
-  if (cache && allowed[dev][slot] >= bytes) return TMGCN_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    set_error("%s: %zu bytes of LDS per block refused", what, bytes);
-    return TMGCN_ERR_LAUNCH;
-  }
-  if (cache) allowed[dev][slot] = bytes;
-  return TMGCN_OK;
-}
-
 inline int64_t egw_cand_count(int64_t N, int T_run) { return (int64_t)T_run * egw_blocks(N) * kEgwL; }
 
 }  // namespace
@@ -582,35 +563,21 @@ extern "C" int64_t tmgcn_egcn_wide_bwd_workspace_bytes(int32_t T_run, int32_t F,
   return (int64_t)T_run * (4LL * F * k + k) * (int64_t)sizeof(double);
 }
 
-static int egw_check(const char* who, int64_t N, int32_t T_run, int32_t F, int32_t k) {
-  TMGCN_REQUIRE(tmgcn_egcn_wide_supported(F, k), "%s: F=%d, k=%d outside 1..%d x 1..%d without 1..%d x 1..%d (tmgcn_egcn_*)", who,
-                F, k, kEgwMax, kEgwMax, kEgNarrowMax, kEgNarrowMax);
-  TMGCN_REQUIRE(T_run >= 0 && T_run <= 65535, "%s: T_run=%d outside 0..65535", who, T_run);
-  TMGCN_REQUIRE(N >= 0 && N < (int64_t)0x7fffffff, "%s: N=%lld outside 0..2^31-2", who, (long long)N);
-  TMGCN_REQUIRE(T_run == 0 || N >= k, "%s: top-k needs N >= k (N=%lld, k=%d) (ef:82)", who, (long long)N, k);
-  TMGCN_REQUIRE((int64_t)T_run * N * F < (int64_t)1 << 62, "%s: T_run x N x F too large", who);
-  return TMGCN_OK;
-}
-
 extern "C" int tmgcn_egcn_wide_fwd(const float* H, const double* P, const double* W0, const int64_t* rowptr,
                                    const int32_t* col, const float* val, const float* X_prev, const double* W_prev,
                                    int32_t F_prev, int32_t* idx, double* ysel, double* Hsel, double* Xg, double* Wseq,
                                    float* W32, double* gates, int64_t N, int32_t T_run, int32_t F, int32_t k,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = egw_check("egcn_wide_fwd", N, T_run, F, k)) return rc;
-  TMGCN_REQUIRE(P && W0 && Wseq, "egcn_wide_fwd: null pointer");
-  TMGCN_REQUIRE(T_run == 0 || (H && idx && ysel && Hsel && Xg && W32), "egcn_wide_fwd: null pointer");
-  TMGCN_REQUIRE(!rowptr || (X_prev && W_prev && F_prev >= 1),
-                "egcn_wide_fwd: the fp64 rows of layer 2 need X_prev, W_prev and F_prev >= 1 (F_prev=%d)", F_prev);
-  TMGCN_REQUIRE(!rowptr || (int64_t)T_run * N * F_prev < (int64_t)1 << 62, "egcn_wide_fwd: T_run x N x F_prev too large");
+  if (int rc = eg_check("egcn_wide_fwd", tmgcn_egcn_wide_supported(F, k), kEgwMax, kEgNarrowMax, N, T_run, F, k,
+                        P && W0 && Wseq, H && idx && ysel && Hsel && Xg && W32))
+    return rc;
+  if (int rc = eg_check_rows("egcn_wide_fwd", rowptr, X_prev && W_prev, F_prev, N, T_run)) return rc;
   hipStream_t st = (hipStream_t)stream;
   double* pre = nullptr;
   if (T_run > 0) {
-    const int64_t need = tmgcn_egcn_wide_fwd_workspace_bytes(N, T_run, F, k);
-    if (!workspace || workspace_bytes < need) {
-      set_error("egcn_wide_fwd: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-      return TMGCN_ERR_WORKSPACE;
-    }
+    if (int rc = check_workspace("egcn_wide_fwd", workspace, workspace_bytes,
+                                 tmgcn_egcn_wide_fwd_workspace_bytes(N, T_run, F, k)))
+      return rc;
     const int64_t nblk = egw_blocks(N);
     double* cs = static_cast<double*>(workspace);
     pre = cs + egw_cand_count(N, T_run);
@@ -629,7 +596,7 @@ extern "C" int tmgcn_egcn_wide_fwd(const float* H, const double* P, const double
     if (int rc = check_launch("egcn_wide_fwd hoist")) return rc;
   }
   const size_t lds = (size_t)(3 * egw_pad(F) * egw_pad(F) + 128) * sizeof(double);
-  if (int rc = egw_allow_lds(egw_chain_fwd_kernel, lds, 0, "egcn_wide_fwd")) return rc;
+  if (int rc = allow_large_lds(egw_chain_fwd_kernel, lds, "egcn_wide_fwd")) return rc;
   hipLaunchKernelGGL(egw_chain_fwd_kernel, dim3((unsigned)k), dim3(64), lds, st, P, W0, pre, (int)T_run, (int)F, (int)k, Wseq,
                      W32, gates);
   return check_launch("egcn_wide_fwd chain");
@@ -639,24 +606,18 @@ extern "C" int tmgcn_egcn_wide_bwd(const double* P, const double* Xg, const int3
                                    const double* Hsel, const double* Wseq, const double* gates, const float* dW32,
                                    const double* dWseq, double* dP, double* dW0, float* dH, int64_t N, int32_t T_run,
                                    int32_t F, int32_t k, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = egw_check("egcn_wide_bwd", N, T_run, F, k)) return rc;
-  TMGCN_REQUIRE(P && Wseq && dP && dW0, "egcn_wide_bwd: null pointer");
-  TMGCN_REQUIRE(T_run == 0 || (Xg && idx && ysel && Hsel && gates), "egcn_wide_bwd: null pointer");
+  if (int rc = eg_check("egcn_wide_bwd", tmgcn_egcn_wide_supported(F, k), kEgwMax, kEgNarrowMax, N, T_run, F, k,
+                        P && Wseq && dP && dW0, Xg && idx && ysel && Hsel && gates))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t need = tmgcn_egcn_wide_bwd_workspace_bytes(T_run, F, k);
-  if (T_run > 0 && (!workspace || workspace_bytes < need)) {
-    set_error("egcn_wide_bwd: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-    return TMGCN_ERR_WORKSPACE;
-  }
-  if (dH && T_run > 0 && hipMemsetAsync(dH, 0, (size_t)T_run * N * F * sizeof(float), st) != hipSuccess) {
-    set_error("egcn_wide_bwd: hipMemsetAsync failed");
-    return TMGCN_ERR_LAUNCH;
-  }
+  if (int rc = eg_bwd_prepare("egcn_wide_bwd", workspace, workspace_bytes, tmgcn_egcn_wide_bwd_workspace_bytes(T_run, F, k), dH,
+                              N, T_run, F, st))
+    return rc;
   const int Fk = F * k;
   double* dA = static_cast<double*>(workspace);
   double* dy = dA + (int64_t)T_run * 4 * Fk;
   const size_t lds = (size_t)(3 * egw_pad(F) * egw_pad(F) + 192) * sizeof(double);
-  if (int rc = egw_allow_lds(egw_chain_bwd_kernel, lds, 1, "egcn_wide_bwd")) return rc;
+  if (int rc = allow_large_lds(egw_chain_bwd_kernel, lds, "egcn_wide_bwd")) return rc;
   hipLaunchKernelGGL(egw_chain_bwd_kernel, dim3((unsigned)k), dim3(64), lds, st, P, Wseq, gates, dW32, dWseq, (int)T_run, (int)F,
                      (int)k, dA, dW0);
   if (int rc = check_launch("egcn_wide_bwd chain")) return rc;

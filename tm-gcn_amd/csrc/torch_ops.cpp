@@ -624,121 +624,113 @@ std::vector<Tensor> widen_params_ad(at::TensorList params) { return WidenFn::app
 bool spmm_gemm_supported(int64_t K, int64_t Nf) { return tmgcn_spmm_gemm_supported((int32_t)K, (int32_t)Nf) != 0; }
 bool layer12_supported(int64_t K0, int64_t F, int64_t Nf) { return tmgcn_layer12_supported((int32_t)K0, (int32_t)F, (int32_t)Nf) != 0; }
 // ---- WD-GCN (wd_gcn_functions.py:66-98): relu(AX·W) + the LSTM recurrence, and its BPTT ----------------------------
+// `wide` selects the kernels of csrc/wdgcn_wide.hip (widths up to 64) through tmgcn_wdgcn_wide_*: the same operator,
+// with an opaque `saved` where the narrow kernels keep the cell states C
 bool wdgcn_supported(int64_t F0, int64_t H) { return tmgcn_wdgcn_supported((int32_t)F0, (int32_t)H) != 0; }
-
-static void wdgcn_check(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
-  want(AX, "wdgcn AX");
-  want(P, "wdgcn P");
-  want(h0, "wdgcn h0");
-  want(c0, "wdgcn c0");
-  TORCH_CHECK(AX.dim() == 3, "wdgcn: AX must be [T, N, F0], got ", AX.sizes());
-  const int64_t F0 = AX.size(2);
-  TORCH_CHECK(tmgcn_wdgcn_supported((int32_t)F0, (int32_t)H), "wdgcn: F0=", F0, ", H=", H,
-              " outside the kernel's widths (1..8 each)");
-  TORCH_CHECK(T_run >= 0 && T_run <= AX.size(0), "wdgcn: T_run=", T_run, " outside 0..", AX.size(0));
-  TORCH_CHECK(P.numel() == tmgcn_wdgcn_param_count((int32_t)F0, (int32_t)H), "wdgcn: P holds ", P.numel(),
-              " floats, the packed parameters of F0=", F0, ", H=", H, " are ", tmgcn_wdgcn_param_count((int32_t)F0, (int32_t)H));
-  TORCH_CHECK(h0.numel() == H && c0.numel() == H, "wdgcn: h0 / c0 must hold H=", H, " values");
-}
-
-// Z [T_run, N, H] and, with need_c, the cell state of every step (what the backward recomputes the gates from)
-std::tuple<Tensor, Tensor> wdgcn_fwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H,
-                                     int64_t T_run, bool need_c) {
-  wdgcn_check(AX, P, h0, c0, H, T_run);
-  c10::DeviceGuard g(AX.device());
-  const int64_t N = AX.size(1);
-  Tensor Z = at::empty({T_run, N, H}, AX.options());
-  Tensor C = need_c ? at::empty({T_run, N, H}, AX.options()) : none_like(AX);
-  ok(tmgcn_wdgcn_fwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
-                         (float*)ptr(Z), need_c ? (float*)ptr(C) : nullptr, N, (int32_t)T_run, (int32_t)AX.size(2),
-                         (int32_t)H, stream_of(AX)),
-     "tmgcn_wdgcn_fwd_f32");
-  return {Z, C};
-}
-
-// dP (packed like P) from dZ [T_run, N, H]
-Tensor wdgcn_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, const Tensor& Z, const Tensor& C,
-                 const Tensor& dZ) {
-  const int64_t H = Z.dim() == 3 ? Z.size(2) : -1, T_run = Z.dim() == 3 ? Z.size(0) : -1;
-  wdgcn_check(AX, P, h0, c0, H, T_run);
-  want(Z, "wdgcn Z");
-  want(C, "wdgcn C");
-  want(dZ, "wdgcn dZ");
-  const int64_t N = AX.size(1), F0 = AX.size(2);
-  TORCH_CHECK(Z.size(1) == N && C.sizes() == Z.sizes() && dZ.sizes() == Z.sizes(), "wdgcn_bwd: Z ", Z.sizes(), ", C ",
-              C.sizes(), ", dZ ", dZ.sizes(), " must all be [T_run, N=", N, ", H]");
-  c10::DeviceGuard g(AX.device());
-  Tensor dP = at::empty({P.numel()}, P.options());
-  const int64_t need = tmgcn_wdgcn_bwd_workspace_bytes(N, (int32_t)F0, (int32_t)H);
-  Tensor ws = at::empty({need > 0 ? need : 1}, AX.options().dtype(at::kByte));
-  ok(tmgcn_wdgcn_bwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
-                         (const float*)ptr(Z), (const float*)ptr(C), (const float*)ptr(dZ), (float*)ptr(dP), N,
-                         (int32_t)T_run, (int32_t)F0, (int32_t)H, ptr(ws), ws.numel(), stream_of(AX)),
-     "tmgcn_wdgcn_bwd_f32");
-  return dP.view(P.sizes());
-}
-
-// ---- WD-GCN at widths up to 64 (csrc/wdgcn_wide.hip): the same operator, `saved` opaque to the caller ----------------
 bool wdgcn_wide_supported(int64_t F0, int64_t H) { return tmgcn_wdgcn_wide_supported((int32_t)F0, (int32_t)H) != 0; }
 
-static void wdgcn_wide_check(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
-  want(AX, "wdgcn_wide AX");
-  want(P, "wdgcn_wide P");
-  want(h0, "wdgcn_wide h0");
-  want(c0, "wdgcn_wide c0");
-  TORCH_CHECK(AX.dim() == 3, "wdgcn_wide: AX must be [T, N, F0], got ", AX.sizes());
+static void wdgcn_check(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run,
+                        bool wide) {
+  const char* who = wide ? "wdgcn_wide" : "wdgcn";
+  want(AX, wide ? "wdgcn_wide AX" : "wdgcn AX");
+  want(P, wide ? "wdgcn_wide P" : "wdgcn P");
+  want(h0, wide ? "wdgcn_wide h0" : "wdgcn h0");
+  want(c0, wide ? "wdgcn_wide c0" : "wdgcn c0");
+  TORCH_CHECK(AX.dim() == 3, who, ": AX must be [T, N, F0], got ", AX.sizes());
   const int64_t F0 = AX.size(2);
-  TORCH_CHECK(tmgcn_wdgcn_wide_supported((int32_t)F0, (int32_t)H), "wdgcn_wide: F0=", F0, ", H=", H,
-              " outside the wide kernels' widths (1..64 each, beyond the narrow kernels' 1..8 x 1..8)");
-  TORCH_CHECK(T_run >= 0 && T_run <= AX.size(0), "wdgcn_wide: T_run=", T_run, " outside 0..", AX.size(0));
-  const int64_t np = F0 * H + 8 * H * H + 4 * H;
-  TORCH_CHECK(P.numel() == np, "wdgcn_wide: P holds ", P.numel(), " floats, the packed parameters of F0=", F0, ", H=", H,
+  if (wide) {
+    TORCH_CHECK(tmgcn_wdgcn_wide_supported((int32_t)F0, (int32_t)H), "wdgcn_wide: F0=", F0, ", H=", H,
+                " outside the wide kernels' widths (1..64 each, beyond the narrow kernels' 1..8 x 1..8)");
+  } else {
+    TORCH_CHECK(tmgcn_wdgcn_supported((int32_t)F0, (int32_t)H), "wdgcn: F0=", F0, ", H=", H,
+                " outside the kernel's widths (1..8 each)");
+  }
+  TORCH_CHECK(T_run >= 0 && T_run <= AX.size(0), who, ": T_run=", T_run, " outside 0..", AX.size(0));
+  const int64_t np = F0 * H + 8 * H * H + 4 * H;               // W | Wf..Wo | Uf..Uo | bf..bo (tmgcn_wdgcn_param_count)
+  TORCH_CHECK(P.numel() == np, who, ": P holds ", P.numel(), " floats, the packed parameters of F0=", F0, ", H=", H,
               " are ", np);
-  TORCH_CHECK(h0.numel() == H && c0.numel() == H, "wdgcn_wide: h0 / c0 must hold H=", H, " values");
+  TORCH_CHECK(h0.numel() == H && c0.numel() == H, who, ": h0 / c0 must hold H=", H, " values");
 }
 
-// Z [T_run, N, H] and, with need_saved, what the backward reads (y, c and the gate activations of every step)
-std::tuple<Tensor, Tensor> wdgcn_wide_fwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H,
-                                          int64_t T_run, bool need_saved) {
-  wdgcn_wide_check(AX, P, h0, c0, H, T_run);
+// Z [T_run, N, H] and, with `need`, what the backward reads: the cell state of every step (narrow: the gates are
+// recomputed from it) or `saved` (wide: y, c and the gate activations of every step)
+static std::tuple<Tensor, Tensor> wdgcn_fwd_any(bool wide, const Tensor& AX, const Tensor& P, const Tensor& h0,
+                                                const Tensor& c0, int64_t H, int64_t T_run, bool need) {
+  wdgcn_check(AX, P, h0, c0, H, T_run, wide);
   c10::DeviceGuard g(AX.device());
   const int64_t N = AX.size(1), F0 = AX.size(2);
   Tensor Z = at::empty({T_run, N, H}, AX.options());
-  Tensor saved = none_like(AX);
-  if (need_saved) {
+  Tensor kept = none_like(AX);
+  if (need && wide) {
     const int64_t bytes = tmgcn_wdgcn_wide_saved_bytes(N, (int32_t)T_run, (int32_t)F0, (int32_t)H);
     TORCH_CHECK(bytes >= 0, "wdgcn_wide_fwd: tmgcn_wdgcn_wide_saved_bytes refused N=", N, ", T_run=", T_run);
-    saved = at::empty({bytes / 4 > 0 ? bytes / 4 : 1}, AX.options());
+    kept = at::empty({bytes / 4 > 0 ? bytes / 4 : 1}, AX.options());
+  } else if (need) {
+    kept = at::empty({T_run, N, H}, AX.options());
   }
-  ok(tmgcn_wdgcn_wide_fwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
-                              (float*)ptr(Z), need_saved ? ptr(saved) : nullptr, N, (int32_t)T_run, (int32_t)F0, (int32_t)H,
-                              stream_of(AX)),
-     "tmgcn_wdgcn_wide_fwd_f32");
-  return {Z, saved};
+  float* kp = need ? (float*)ptr(kept) : nullptr;
+  if (wide)
+    ok(tmgcn_wdgcn_wide_fwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
+                                (float*)ptr(Z), kp, N, (int32_t)T_run, (int32_t)F0, (int32_t)H, stream_of(AX)),
+       "tmgcn_wdgcn_wide_fwd_f32");
+  else
+    ok(tmgcn_wdgcn_fwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
+                           (float*)ptr(Z), kp, N, (int32_t)T_run, (int32_t)F0, (int32_t)H, stream_of(AX)),
+       "tmgcn_wdgcn_fwd_f32");
+  return {Z, kept};
+}
+std::tuple<Tensor, Tensor> wdgcn_fwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H,
+                                     int64_t T_run, bool need_c) {
+  return wdgcn_fwd_any(false, AX, P, h0, c0, H, T_run, need_c);
+}
+std::tuple<Tensor, Tensor> wdgcn_wide_fwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H,
+                                          int64_t T_run, bool need_saved) {
+  return wdgcn_fwd_any(true, AX, P, h0, c0, H, T_run, need_saved);
 }
 
-// dP (packed like P) from dZ [T_run, N, H]
-Tensor wdgcn_wide_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, const Tensor& Z,
-                      const Tensor& saved, const Tensor& dZ) {
+// dP (packed like P) from dZ [T_run, N, H]; `kept`: the forward's second result
+static Tensor wdgcn_bwd_any(bool wide, const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, const Tensor& Z,
+                            const Tensor& kept, const Tensor& dZ) {
   const int64_t H = Z.dim() == 3 ? Z.size(2) : -1, T_run = Z.dim() == 3 ? Z.size(0) : -1;
-  wdgcn_wide_check(AX, P, h0, c0, H, T_run);
-  want(Z, "wdgcn_wide Z");
-  want(saved, "wdgcn_wide saved");
-  want(dZ, "wdgcn_wide dZ");
+  wdgcn_check(AX, P, h0, c0, H, T_run, wide);
+  want(Z, wide ? "wdgcn_wide Z" : "wdgcn Z");
+  want(kept, wide ? "wdgcn_wide saved" : "wdgcn C");
+  want(dZ, wide ? "wdgcn_wide dZ" : "wdgcn dZ");
   const int64_t N = AX.size(1), F0 = AX.size(2);
-  TORCH_CHECK(Z.size(1) == N && dZ.sizes() == Z.sizes(), "wdgcn_wide_bwd: Z ", Z.sizes(), ", dZ ", dZ.sizes(),
-              " must both be [T_run, N=", N, ", H]");
-  const int64_t sbytes = tmgcn_wdgcn_wide_saved_bytes(N, (int32_t)T_run, (int32_t)F0, (int32_t)H);
-  TORCH_CHECK(saved.numel() * 4 >= sbytes, "wdgcn_wide_bwd: saved holds ", saved.numel() * 4, " bytes, ", sbytes, " needed");
+  int64_t need;
+  if (wide) {
+    TORCH_CHECK(Z.size(1) == N && dZ.sizes() == Z.sizes(), "wdgcn_wide_bwd: Z ", Z.sizes(), ", dZ ", dZ.sizes(),
+                " must both be [T_run, N=", N, ", H]");
+    const int64_t sbytes = tmgcn_wdgcn_wide_saved_bytes(N, (int32_t)T_run, (int32_t)F0, (int32_t)H);
+    TORCH_CHECK(kept.numel() * 4 >= sbytes, "wdgcn_wide_bwd: saved holds ", kept.numel() * 4, " bytes, ", sbytes, " needed");
+    need = tmgcn_wdgcn_wide_bwd_workspace_bytes(N, (int32_t)T_run, (int32_t)F0, (int32_t)H);
+  } else {
+    TORCH_CHECK(Z.size(1) == N && kept.sizes() == Z.sizes() && dZ.sizes() == Z.sizes(), "wdgcn_bwd: Z ", Z.sizes(), ", C ",
+                kept.sizes(), ", dZ ", dZ.sizes(), " must all be [T_run, N=", N, ", H]");
+    need = tmgcn_wdgcn_bwd_workspace_bytes(N, (int32_t)F0, (int32_t)H);
+  }
   c10::DeviceGuard g(AX.device());
   Tensor dP = at::empty({P.numel()}, P.options());
-  const int64_t need = tmgcn_wdgcn_wide_bwd_workspace_bytes(N, (int32_t)T_run, (int32_t)F0, (int32_t)H);
   Tensor ws = at::empty({need > 0 ? need : 1}, AX.options().dtype(at::kByte));
-  ok(tmgcn_wdgcn_wide_bwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
-                              (const float*)ptr(Z), ptr(saved), (const float*)ptr(dZ), (float*)ptr(dP), N, (int32_t)T_run,
-                              (int32_t)F0, (int32_t)H, ptr(ws), ws.numel(), stream_of(AX)),
-     "tmgcn_wdgcn_wide_bwd_f32");
+  if (wide)
+    ok(tmgcn_wdgcn_wide_bwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
+                                (const float*)ptr(Z), ptr(kept), (const float*)ptr(dZ), (float*)ptr(dP), N, (int32_t)T_run,
+                                (int32_t)F0, (int32_t)H, ptr(ws), ws.numel(), stream_of(AX)),
+       "tmgcn_wdgcn_wide_bwd_f32");
+  else
+    ok(tmgcn_wdgcn_bwd_f32((const float*)ptr(AX), (const float*)ptr(P), (const float*)ptr(h0), (const float*)ptr(c0),
+                           (const float*)ptr(Z), (const float*)ptr(kept), (const float*)ptr(dZ), (float*)ptr(dP), N,
+                           (int32_t)T_run, (int32_t)F0, (int32_t)H, ptr(ws), ws.numel(), stream_of(AX)),
+       "tmgcn_wdgcn_bwd_f32");
   return dP.view(P.sizes());
+}
+Tensor wdgcn_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, const Tensor& Z, const Tensor& C,
+                 const Tensor& dZ) {
+  return wdgcn_bwd_any(false, AX, P, h0, c0, Z, C, dZ);
+}
+Tensor wdgcn_wide_bwd(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, const Tensor& Z,
+                      const Tensor& saved, const Tensor& dZ) {
+  return wdgcn_bwd_any(true, AX, P, h0, c0, Z, saved, dZ);
 }
 
 // ---- EvolveGCN-H (evolvegcn_functions.py:80-95): top-k summary + matrix-GRU weight evolution, and its backward ------
@@ -1251,36 +1243,20 @@ struct Layer12Fn : public torch::autograd::Function<Layer12Fn> {
 // packed parameters P only (AX, h_init, c_init are constants of the reference's model: wgf:52-53, 80-84)
 struct WdgcnLstmFn : public torch::autograd::Function<WdgcnLstmFn> {
   static Tensor forward(AutogradContext* ctx, const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0,
-                        int64_t H, int64_t T_run, bool need) {
+                        int64_t H, int64_t T_run, bool need, bool wide) {
     at::AutoDispatchBelowADInplaceOrView guard;
-    auto [Z, C] = wdgcn_fwd(AX, P, h0, c0, H, T_run, need);
-    if (need) ctx->save_for_backward({AX, P, h0, c0, Z, C});
+    auto [Z, kept] = wdgcn_fwd_any(wide, AX, P, h0, c0, H, T_run, need);
+    if (need) ctx->save_for_backward({AX, P, h0, c0, Z, kept});
+    ctx->saved_data["wide"] = wide;
     return Z;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto sv = ctx->get_saved_variables();
     Tensor dZ = grads[0].defined() ? grads[0].contiguous() : at::zeros_like(sv[4]);
-    return {Tensor(), wdgcn_bwd(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], dZ), Tensor(), Tensor(), Tensor(), Tensor(),
-            Tensor()};
-  }
-};
-
-// the same operator through the wide kernels (widths up to 64)
-struct WdgcnWideLstmFn : public torch::autograd::Function<WdgcnWideLstmFn> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0,
-                        int64_t H, int64_t T_run, bool need) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    auto [Z, saved] = wdgcn_wide_fwd(AX, P, h0, c0, H, T_run, need);
-    if (need) ctx->save_for_backward({AX, P, h0, c0, Z, saved});
-    return Z;
-  }
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    auto sv = ctx->get_saved_variables();
-    Tensor dZ = grads[0].defined() ? grads[0].contiguous() : at::zeros_like(sv[4]);
-    return {Tensor(), wdgcn_wide_bwd(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], dZ), Tensor(), Tensor(), Tensor(), Tensor(),
-            Tensor()};
+    variable_list out(8);
+    out[1] = wdgcn_bwd_any(ctx->saved_data["wide"].toBool(), sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], dZ);
+    return out;
   }
 };
 
@@ -1413,17 +1389,18 @@ Tensor layer12_ad(const Tensor& H, const Tensor& W1, const Tensor& W2, const Ten
                           grad && W1.requires_grad(), grad && W2.requires_grad());
 }
 Tensor activation_ad(const Tensor& x, int64_t act) { return ActivationFn::apply(x, act); }
-Tensor wdgcn_lstm_ad(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
+static Tensor wdgcn_lstm_any(bool wide, const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H,
+                             int64_t T_run) {
   const bool grad = at::GradMode::is_enabled();
   TORCH_CHECK(!(grad && (AX.requires_grad() || h0.requires_grad() || c0.requires_grad())),
-              "wdgcn_lstm: AX, h_init and c_init are constants (no gradient is formed for them)");
-  return WdgcnLstmFn::apply(AX, P, h0, c0, H, T_run, grad && P.requires_grad());
+              wide ? "wdgcn_lstm_wide" : "wdgcn_lstm", ": AX, h_init and c_init are constants (no gradient is formed for them)");
+  return WdgcnLstmFn::apply(AX, P, h0, c0, H, T_run, grad && P.requires_grad(), wide);
+}
+Tensor wdgcn_lstm_ad(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
+  return wdgcn_lstm_any(false, AX, P, h0, c0, H, T_run);
 }
 Tensor wdgcn_lstm_wide_ad(const Tensor& AX, const Tensor& P, const Tensor& h0, const Tensor& c0, int64_t H, int64_t T_run) {
-  const bool grad = at::GradMode::is_enabled();
-  TORCH_CHECK(!(grad && (AX.requires_grad() || h0.requires_grad() || c0.requires_grad())),
-              "wdgcn_lstm_wide: AX, h_init and c_init are constants (no gradient is formed for them)");
-  return WdgcnWideLstmFn::apply(AX, P, h0, c0, H, T_run, grad && P.requires_grad());
+  return wdgcn_lstm_any(true, AX, P, h0, c0, H, T_run);
 }
 static std::tuple<Tensor, Tensor> egcn_evolve_any(bool wide, const Tensor& H, const Tensor& p, at::TensorList gates,
                                                   const Tensor& W0, int64_t k, int64_t T_run, const OptTensor& rowptr,
@@ -1541,6 +1518,24 @@ TORCH_LIBRARY(tmgcn, m) {
         "Tensor? col=None, Tensor? val=None, Tensor? X_prev=None, Tensor? W_prev=None) -> (Tensor, Tensor)");
 }
 
+// the differentiable operators, registered alike under every key that implements them
+static void impl_differentiable(torch::Library& m) {
+  m.impl("m_transform", &m_transform_ad);
+  m.impl("spmm", &spmm_ad);
+  m.impl("feature_gemm", &feature_gemm_ad);
+  m.impl("spmm_feature_gemm", &spmm_feature_gemm_ad);
+  m.impl("edge_head", &edge_head_ad);
+  m.impl("activation", &activation_ad);
+  m.impl("layer12", &layer12_ad);
+  m.impl("widen_params", &widen_params_ad);
+  m.impl("weighted_ce", &weighted_ce_ad);
+  m.impl("head_loss", &head_loss_ad);
+  m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
+  m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
+  m.impl("egcn_evolve", &egcn_evolve_ad);
+  m.impl("egcn_evolve_wide", &egcn_evolve_wide_ad);
+}
+
 // ROCm tensors carry the CUDA dispatch key in PyTorch-ROCm
 TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("mtransform", &mtransform);
@@ -1572,37 +1567,11 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("egcn_wide_bwd", &egcn_wide_bwd);
   // below the Autograd key (inference mode, or called from inside another autograd node) the
   // differentiable operators are their plain forwards
-  m.impl("m_transform", &m_transform_ad);
-  m.impl("spmm", &spmm_ad);
-  m.impl("feature_gemm", &feature_gemm_ad);
-  m.impl("spmm_feature_gemm", &spmm_feature_gemm_ad);
-  m.impl("edge_head", &edge_head_ad);
-  m.impl("activation", &activation_ad);
-  m.impl("layer12", &layer12_ad);
-  m.impl("widen_params", &widen_params_ad);
-  m.impl("weighted_ce", &weighted_ce_ad);
-  m.impl("head_loss", &head_loss_ad);
-  m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
-  m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
-  m.impl("egcn_evolve", &egcn_evolve_ad);
-  m.impl("egcn_evolve_wide", &egcn_evolve_wide_ad);
+  impl_differentiable(m);
 }
 
 TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
-  m.impl("m_transform", &m_transform_ad);
-  m.impl("spmm", &spmm_ad);
-  m.impl("feature_gemm", &feature_gemm_ad);
-  m.impl("spmm_feature_gemm", &spmm_feature_gemm_ad);
-  m.impl("edge_head", &edge_head_ad);
-  m.impl("activation", &activation_ad);
-  m.impl("layer12", &layer12_ad);
-  m.impl("widen_params", &widen_params_ad);
-  m.impl("weighted_ce", &weighted_ce_ad);
-  m.impl("head_loss", &head_loss_ad);
-  m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
-  m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
-  m.impl("egcn_evolve", &egcn_evolve_ad);
-  m.impl("egcn_evolve_wide", &egcn_evolve_wide_ad);
+  impl_differentiable(m);
 }
 
 // a CPU tensor reaching a kernel-level op gets the reference-style RuntimeError, not "no kernel"
@@ -1615,18 +1584,5 @@ TORCH_LIBRARY_IMPL(tmgcn, CPU, m) {
   m.impl("edge_head_fwd", &edge_head_fwd);
   m.impl("act_fwd", &act_fwd);
   m.impl("act_bwd", &act_bwd);
-  m.impl("m_transform", &m_transform_ad);
-  m.impl("spmm", &spmm_ad);
-  m.impl("feature_gemm", &feature_gemm_ad);
-  m.impl("spmm_feature_gemm", &spmm_feature_gemm_ad);
-  m.impl("edge_head", &edge_head_ad);
-  m.impl("activation", &activation_ad);
-  m.impl("layer12", &layer12_ad);
-  m.impl("widen_params", &widen_params_ad);
-  m.impl("weighted_ce", &weighted_ce_ad);
-  m.impl("head_loss", &head_loss_ad);
-  m.impl("wdgcn_lstm", &wdgcn_lstm_ad);
-  m.impl("wdgcn_lstm_wide", &wdgcn_lstm_wide_ad);
-  m.impl("egcn_evolve", &egcn_evolve_ad);
-  m.impl("egcn_evolve_wide", &egcn_evolve_wide_ad);
+  impl_differentiable(m);
 }

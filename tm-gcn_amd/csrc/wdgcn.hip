@@ -22,6 +22,7 @@
 // reduced across the wave's node groups with xor shuffles and written as one row of a per-wave slab; a second launch
 // sums the rows in row order in fp64.  No atomics: two runs give the same bits.
 #include "common.h"
+#include "wdgcn_layout.h"   // wd_params, WdOff, wd_sigmoid
 
 namespace tmgcn {
 namespace {
@@ -32,19 +33,10 @@ constexpr int kWdPF = 8;            // steps whose inputs are in flight ahead of
 constexpr int kWdMaxRows = 1024;    // waves (= slab rows) of the backward
 
 __host__ __device__ constexpr int wd_group(int H) { return H <= 1 ? 1 : H <= 2 ? 2 : H <= 4 ? 4 : 8; }
-__host__ __device__ constexpr int64_t wd_params(int F0, int H) { return (int64_t)F0 * H + 8LL * H * H + 4LL * H; }
 inline int64_t wd_rows(int64_t N, int H) {
   const int64_t groups = (N + 64 / wd_group(H) - 1) / (64 / wd_group(H));
   return groups < kWdMaxRows ? groups : kWdMaxRows;
 }
-
-__device__ __forceinline__ float wd_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
-// Packed parameters P (the order of wgf:36-51): W [F0][H] | Wf Wj Wc Wo [H][H] | Uf Uj Uc Uo [H][H] | bf bj bc bo [H]
-struct WdOff {
-  int w, wg, ug, b;
-  __device__ __forceinline__ WdOff(int F0, int H) : w(0), wg(F0 * H), ug(F0 * H + 4 * H * H), b(F0 * H + 8 * H * H) {}
-};
 
 // this lane's unit u: its column of W (w[i] = W[i][u]), of every gate matrix (wg[g][k] = Wg[k][u], ug[g][k] = Ug[k][u])
 // and its biases; zero for the padding lanes u >= H
@@ -317,6 +309,21 @@ int wd_bwd(const float* AX, const float* P, const float* h0, const float* c0, co
   return check_launch("wdgcn_bwd slab sum");
 }
 
+// f(std::integral_constant<int, H>) for the run-time H of 1..kWdMaxH: the kernels are instantiated per width
+template <typename F>
+int wd_dispatch(int H, F f) {
+  switch (H) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
 }  // namespace
 }  // namespace tmgcn
 
@@ -335,34 +342,27 @@ extern "C" int64_t tmgcn_wdgcn_bwd_workspace_bytes(int64_t N, int32_t F0, int32_
   return N == 0 ? 0 : wd_rows(N, H) * wd_params(F0, H) * (int64_t)sizeof(float);
 }
 
+static int wd_check(const char* who, int64_t N, int32_t T_run, int32_t F0, int32_t H) {
+  TMGCN_REQUIRE(tmgcn_wdgcn_supported(F0, H), "%s: F0=%d, H=%d outside 1..%d x 1..%d", who, F0, H, kWdMaxF, kWdMaxH);
+  TMGCN_REQUIRE(N >= 0 && T_run >= 0, "%s: negative size (N=%lld, T_run=%d)", who, (long long)N, T_run);
+  TMGCN_REQUIRE(N < (int64_t)1 << 31 && (int64_t)T_run * N * (H > F0 ? H : F0) < (int64_t)1 << 62,
+                "%s: N=%lld too large", who, (long long)N);
+  return TMGCN_OK;
+}
+
 extern "C" int tmgcn_wdgcn_fwd_f32(const float* AX, const float* P, const float* h0, const float* c0, float* Z, float* C,
                                    int64_t N, int32_t T_run, int32_t F0, int32_t H, void* stream) {
-  TMGCN_REQUIRE(tmgcn_wdgcn_supported(F0, H), "wdgcn_fwd: F0=%d, H=%d outside 1..%d x 1..%d", F0, H, kWdMaxF, kWdMaxH);
-  TMGCN_REQUIRE(N >= 0 && T_run >= 0, "wdgcn_fwd: negative size (N=%lld, T_run=%d)", (long long)N, T_run);
-  TMGCN_REQUIRE(N < (int64_t)1 << 31 && (int64_t)T_run * N * (H > F0 ? H : F0) < (int64_t)1 << 62,
-                "wdgcn_fwd: N=%lld too large", (long long)N);
+  if (int rc = wd_check("wdgcn_fwd", N, T_run, F0, H)) return rc;
   if (N == 0 || T_run == 0) return TMGCN_OK;
   TMGCN_REQUIRE(AX && P && h0 && c0 && Z, "wdgcn_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  switch (H) {
-    case 1: return wd_fwd<1>(AX, P, h0, c0, Z, C, N, T_run, F0, st);
-    case 2: return wd_fwd<2>(AX, P, h0, c0, Z, C, N, T_run, F0, st);
-    case 3: return wd_fwd<3>(AX, P, h0, c0, Z, C, N, T_run, F0, st);
-    case 4: return wd_fwd<4>(AX, P, h0, c0, Z, C, N, T_run, F0, st);
-    case 5: return wd_fwd<5>(AX, P, h0, c0, Z, C, N, T_run, F0, st);
-    case 6: return wd_fwd<6>(AX, P, h0, c0, Z, C, N, T_run, F0, st);
-    case 7: return wd_fwd<7>(AX, P, h0, c0, Z, C, N, T_run, F0, st);
-    default: return wd_fwd<8>(AX, P, h0, c0, Z, C, N, T_run, F0, st);
-  }
+  return wd_dispatch(H, [&](auto h) { return wd_fwd<decltype(h)::value>(AX, P, h0, c0, Z, C, N, T_run, F0, st); });
 }
 
 extern "C" int tmgcn_wdgcn_bwd_f32(const float* AX, const float* P, const float* h0, const float* c0, const float* Z,
                                    const float* C, const float* dZ, float* dP, int64_t N, int32_t T_run, int32_t F0,
                                    int32_t H, void* workspace, int64_t workspace_bytes, void* stream) {
-  TMGCN_REQUIRE(tmgcn_wdgcn_supported(F0, H), "wdgcn_bwd: F0=%d, H=%d outside 1..%d x 1..%d", F0, H, kWdMaxF, kWdMaxH);
-  TMGCN_REQUIRE(N >= 0 && T_run >= 0, "wdgcn_bwd: negative size (N=%lld, T_run=%d)", (long long)N, T_run);
-  TMGCN_REQUIRE(N < (int64_t)1 << 31 && (int64_t)T_run * N * (H > F0 ? H : F0) < (int64_t)1 << 62,
-                "wdgcn_bwd: N=%lld too large", (long long)N);
+  if (int rc = wd_check("wdgcn_bwd", N, T_run, F0, H)) return rc;
   TMGCN_REQUIRE(dP, "wdgcn_bwd: null dP");
   hipStream_t st = (hipStream_t)stream;
   if (N == 0 || T_run == 0) {                                      // nothing ran: every gradient is zero
@@ -373,20 +373,9 @@ extern "C" int tmgcn_wdgcn_bwd_f32(const float* AX, const float* P, const float*
     return TMGCN_OK;
   }
   TMGCN_REQUIRE(AX && P && h0 && c0 && Z && C && dZ, "wdgcn_bwd: null pointer");
-  const int64_t need = tmgcn_wdgcn_bwd_workspace_bytes(N, F0, H);
-  if (!workspace || workspace_bytes < need) {
-    set_error("wdgcn_bwd: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-    return TMGCN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace("wdgcn_bwd", workspace, workspace_bytes, tmgcn_wdgcn_bwd_workspace_bytes(N, F0, H))) return rc;
   float* slab = static_cast<float*>(workspace);
-  switch (H) {
-    case 1: return wd_bwd<1>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
-    case 2: return wd_bwd<2>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
-    case 3: return wd_bwd<3>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
-    case 4: return wd_bwd<4>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
-    case 5: return wd_bwd<5>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
-    case 6: return wd_bwd<6>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
-    case 7: return wd_bwd<7>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
-    default: return wd_bwd<8>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
-  }
+  return wd_dispatch(H, [&](auto h) {
+    return wd_bwd<decltype(h)::value>(AX, P, h0, c0, Z, C, dZ, dP, N, T_run, F0, slab, st);
+  });
 }

@@ -27,6 +27,7 @@
 // waves than SIMDs, so no other wave fills the gap.  At H = 64 the 128 KB weight image admits one block per CU.
 // Measured: DESIGN.md §4 "WD-GCN, wide", profiles/wdgcn_wide_epoch.json.
 #include "common.h"
+#include "wdgcn_layout.h"   // wd_params, wd_sigmoid
 
 namespace tmgcn {
 namespace {
@@ -39,7 +40,6 @@ constexpr int kWwPF = 4;            // steps whose AX rows are in flight
 constexpr int kWwMaxSlabs = 512;    // blocks (= slab rows) of the parameter-gradient kernel
 constexpr int kWwSlabRows = 256;    // rows a parameter-gradient block takes at least
 
-__host__ __device__ constexpr int64_t ww_params(int F0, int H) { return (int64_t)F0 * H + 8LL * H * H + 4LL * H; }
 inline int ww_tiles(int H) { return (H + 15) / 16; }
 inline int ww_slabs(int64_t R) {
   const int64_t b = (R + kWwSlabRows - 1) / kWwSlabRows;
@@ -53,7 +53,6 @@ inline size_t ww_bwd_lds(int NT) {
   return (size_t)(2 * NT * 4 * 4 * NT) * 64 * sizeof(float);
 }
 
-__device__ __forceinline__ float ww_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ f32x4 ww_mfma(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -111,6 +110,8 @@ __global__ __launch_bounds__(256) void wdgcn_wide_fwd_kernel(const float* __rest
   float* Gs = ww_lds;                             // [NT][4][KS][64]: gate g, output tile mt
   float* Ws = Gs + NT * 4 * KS * 64;              // [NT][4·nj][64]
   float* Bs = Ws + NT * 4 * nj * 64;              // [4][16·NT]: the biases, zero past H
+  // WdOff's offsets (wdgcn_layout.h), written out here and in the two kernels below: through the struct these kernels
+  // compile to different code
   const int off_wg = F0 * H, off_ug = off_wg + 4 * H * H, off_b = off_ug + 4 * H * H;
   for (int i = threadIdx.x; i < NT * 4 * KS * 64; i += 256) {
     const int l = i & 63, ks = (i >> 6) % KS, g = ((i >> 6) / KS) & 3, mt = (i >> 6) / (KS * 4);
@@ -216,10 +217,10 @@ __global__ __launch_bounds__(256) void wdgcn_wide_fwd_kernel(const float* __rest
         f32x4 gf, gj, gc, go;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          gf[e] = ww_sigmoid(acc[0][mt][e]);
-          gj[e] = ww_sigmoid(acc[1][mt][e]);
-          gc[e] = ww_sigmoid(acc[2][mt][e]);
-          go[e] = ww_sigmoid(acc[3][mt][e]);
+          gf[e] = wd_sigmoid(acc[0][mt][e]);
+          gj[e] = wd_sigmoid(acc[1][mt][e]);
+          gc[e] = wd_sigmoid(acc[2][mt][e]);
+          go[e] = wd_sigmoid(acc[3][mt][e]);
           const float cn = gj[e] * gc[e] + gf[e] * c[mt][e];       // wgf:94
           c[mt][e] = cn;
           h[mt][e] = u0 + e < H ? go[e] * tanhf(cn) : 0.f;         // wgf:95; padding units stay zero
@@ -408,7 +409,7 @@ __global__ __launch_bounds__(256) void wdgcn_wide_dparam_kernel(const float* __r
     }
   }
 
-  float* out = slab + (int64_t)blockIdx.x * ww_params(F0, H);
+  float* out = slab + (int64_t)blockIdx.x * wd_params(F0, H);
   const int off_wg = F0 * H, off_ug = off_wg + 4 * H * H, off_b = off_ug + 4 * H * H;
 #pragma unroll
   for (int mu = 0; mu < NT; ++mu) {
@@ -454,32 +455,13 @@ __global__ __launch_bounds__(256) void wdgcn_wide_slab_sum_kernel(const float* _
   dP[j] = (float)s;
 }
 
-// a block may use more than 64 KB of LDS only after the kernel has been told so: once per kernel, device and host thread
-template <typename K>
-int ww_allow_lds(K kernel, size_t bytes, int slot, const char* what) {
-  if (bytes <= 64 * 1024) return TMGCN_OK;
-  thread_local size_t allowed[16][8] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  const bool cache = dev >= 0 && dev < 16;
-  if (cache && allowed[dev][slot] >= bytes) return TMGCN_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    set_error("%s: %zu bytes of LDS per block refused", what, bytes);
-    return TMGCN_ERR_LAUNCH;
-  }
-  if (cache) allowed[dev][slot] = bytes;
-  return TMGCN_OK;
-}
-
 inline bool ww_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int NT>
 int ww_fwd(const float* AX, const float* P, const float* h0, const float* c0, float* Z, float* saved, int64_t N, int T_run,
            int F0, int H, hipStream_t st) {
   const size_t lds = ww_fwd_lds(F0, H);
-  int rc = ww_allow_lds(wdgcn_wide_fwd_kernel<NT>, lds, NT - 1, "wdgcn_wide_fwd");
+  int rc = allow_large_lds(wdgcn_wide_fwd_kernel<NT>, lds, "wdgcn_wide_fwd");
   if (rc) return rc;
   const int vec_ax = F0 % 4 == 0 && ww_aligned16(AX);
   const int vec_h = H % 4 == 0 && ww_aligned16(Z) && ww_aligned16(saved);
@@ -496,7 +478,7 @@ int ww_bwd(const float* AX, const float* P, const float* h0, const float* c0, co
   // the padding tile only multiplies zeros
   constexpr int NB = NT == 3 ? 4 : NT;
   const size_t lds = ww_bwd_lds(NB);
-  int rc = ww_allow_lds(wdgcn_wide_bwd_kernel<NB>, lds, 4 + NB - 1, "wdgcn_wide_bwd");
+  int rc = allow_large_lds(wdgcn_wide_bwd_kernel<NB>, lds, "wdgcn_wide_bwd");
   if (rc) return rc;
   const int64_t R = (int64_t)T_run * N;
   float* dG = ws;
@@ -513,9 +495,20 @@ int ww_bwd(const float* AX, const float* P, const float* h0, const float* c0, co
                      H);
   rc = check_launch("wdgcn_wide_bwd parameter gradients");
   if (rc) return rc;
-  const int np = (int)ww_params(F0, H);
+  const int np = (int)wd_params(F0, H);
   hipLaunchKernelGGL(wdgcn_wide_slab_sum_kernel, dim3((np + 255) / 256), dim3(256), 0, st, slab, dP, rows, np);
   return check_launch("wdgcn_wide_bwd slab sum");
+}
+
+// f(std::integral_constant<int, NT>) for the NT = ww_tiles(H) of 1..4 unit tiles: the kernels are instantiated per NT
+template <typename F>
+int ww_dispatch(int H, F f) {
+  switch (ww_tiles(H)) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
 }
 
 }  // namespace
@@ -536,38 +529,35 @@ extern "C" int64_t tmgcn_wdgcn_wide_bwd_workspace_bytes(int64_t N, int32_t T_run
   if (!tmgcn_wdgcn_wide_supported(F0, H) || N < 0 || T_run < 0) return -1;
   const int64_t R = (int64_t)T_run * N;
   if (R == 0) return 0;
-  return (5 * R * H + ww_slabs(R) * ww_params(F0, H)) * (int64_t)sizeof(float);
+  return (5 * R * H + ww_slabs(R) * wd_params(F0, H)) * (int64_t)sizeof(float);
 }
 
-#define WW_REQUIRE_SHAPE(who)                                                                                              \
-  TMGCN_REQUIRE(tmgcn_wdgcn_wide_supported(F0, H), who ": F0=%d, H=%d outside the wide kernels' widths (1..%d x 1..%d, "  \
-                "beyond the narrow kernels' 1..8 x 1..8)", F0, H, kWwMaxF, kWwMaxH);                                       \
-  TMGCN_REQUIRE(N >= 0 && T_run >= 0, who ": negative size (N=%lld, T_run=%d)", (long long)N, T_run);                      \
-  TMGCN_REQUIRE(N < (int64_t)1 << 31 && (int64_t)T_run * N < (int64_t)1 << 48, who ": N=%lld too large", (long long)N)
+static int ww_check(const char* who, int64_t N, int32_t T_run, int32_t F0, int32_t H) {
+  TMGCN_REQUIRE(tmgcn_wdgcn_wide_supported(F0, H), "%s: F0=%d, H=%d outside the wide kernels' widths (1..%d x 1..%d, "
+                "beyond the narrow kernels' 1..8 x 1..8)", who, F0, H, kWwMaxF, kWwMaxH);
+  TMGCN_REQUIRE(N >= 0 && T_run >= 0, "%s: negative size (N=%lld, T_run=%d)", who, (long long)N, T_run);
+  TMGCN_REQUIRE(N < (int64_t)1 << 31 && (int64_t)T_run * N < (int64_t)1 << 48, "%s: N=%lld too large", who, (long long)N);
+  return TMGCN_OK;
+}
 
 extern "C" int tmgcn_wdgcn_wide_fwd_f32(const float* AX, const float* P, const float* h0, const float* c0, float* Z,
                                         void* saved, int64_t N, int32_t T_run, int32_t F0, int32_t H, void* stream) {
-  WW_REQUIRE_SHAPE("wdgcn_wide_fwd");
+  if (int rc = ww_check("wdgcn_wide_fwd", N, T_run, F0, H)) return rc;
   if (N == 0 || T_run == 0) return TMGCN_OK;
   TMGCN_REQUIRE(AX && P && h0 && c0 && Z, "wdgcn_wide_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   float* sv = static_cast<float*>(saved);
-  switch (ww_tiles(H)) {
-    case 1: return ww_fwd<1>(AX, P, h0, c0, Z, sv, N, T_run, F0, H, st);
-    case 2: return ww_fwd<2>(AX, P, h0, c0, Z, sv, N, T_run, F0, H, st);
-    case 3: return ww_fwd<3>(AX, P, h0, c0, Z, sv, N, T_run, F0, H, st);
-    default: return ww_fwd<4>(AX, P, h0, c0, Z, sv, N, T_run, F0, H, st);
-  }
+  return ww_dispatch(H, [&](auto nt) { return ww_fwd<decltype(nt)::value>(AX, P, h0, c0, Z, sv, N, T_run, F0, H, st); });
 }
 
 extern "C" int tmgcn_wdgcn_wide_bwd_f32(const float* AX, const float* P, const float* h0, const float* c0, const float* Z,
                                         const void* saved, const float* dZ, float* dP, int64_t N, int32_t T_run, int32_t F0,
                                         int32_t H, void* workspace, int64_t workspace_bytes, void* stream) {
-  WW_REQUIRE_SHAPE("wdgcn_wide_bwd");
+  if (int rc = ww_check("wdgcn_wide_bwd", N, T_run, F0, H)) return rc;
   TMGCN_REQUIRE(dP, "wdgcn_wide_bwd: null dP");
   hipStream_t st = (hipStream_t)stream;
   if (N == 0 || T_run == 0) {                                      // nothing ran: every gradient is zero
-    if (hipMemsetAsync(dP, 0, ww_params(F0, H) * sizeof(float), st) != hipSuccess) {
+    if (hipMemsetAsync(dP, 0, wd_params(F0, H) * sizeof(float), st) != hipSuccess) {
       set_error("wdgcn_wide_bwd: hipMemsetAsync failed");
       return TMGCN_ERR_LAUNCH;
     }
@@ -575,17 +565,12 @@ extern "C" int tmgcn_wdgcn_wide_bwd_f32(const float* AX, const float* P, const f
   }
   TMGCN_REQUIRE(AX && P && h0 && c0 && Z && dZ, "wdgcn_wide_bwd: null pointer");
   TMGCN_REQUIRE(saved, "wdgcn_wide_bwd: null saved (the forward must run with a saved buffer)");
-  const int64_t need = tmgcn_wdgcn_wide_bwd_workspace_bytes(N, T_run, F0, H);
-  if (!workspace || workspace_bytes < need) {
-    set_error("wdgcn_wide_bwd: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-    return TMGCN_ERR_WORKSPACE;
-  }
+  if (int rc = check_workspace("wdgcn_wide_bwd", workspace, workspace_bytes,
+                               tmgcn_wdgcn_wide_bwd_workspace_bytes(N, T_run, F0, H)))
+    return rc;
   const float* sv = static_cast<const float*>(saved);
   float* ws = static_cast<float*>(workspace);
-  switch (ww_tiles(H)) {
-    case 1: return ww_bwd<1>(AX, P, h0, c0, Z, sv, dZ, dP, N, T_run, F0, H, ws, st);
-    case 2: return ww_bwd<2>(AX, P, h0, c0, Z, sv, dZ, dP, N, T_run, F0, H, ws, st);
-    case 3: return ww_bwd<3>(AX, P, h0, c0, Z, sv, dZ, dP, N, T_run, F0, H, ws, st);
-    default: return ww_bwd<4>(AX, P, h0, c0, Z, sv, dZ, dP, N, T_run, F0, H, ws, st);
-  }
+  return ww_dispatch(H, [&](auto nt) {
+    return ww_bwd<decltype(nt)::value>(AX, P, h0, c0, Z, sv, dZ, dP, N, T_run, F0, H, ws, st);
+  });
 }

@@ -699,35 +699,30 @@ def activation(x: torch.Tensor, act) -> torch.Tensor:
 WDGCN_PARAM_NAMES = ("W", "Wf", "Wj", "Wc", "Wo", "Uf", "Uj", "Uc", "Uo", "bf", "bj", "bc", "bo")   # wgf:36-51, in order
 
 
-@functools.lru_cache(maxsize=None)
-def _wdgcn_widths_ok(F0: int, H: int) -> bool:
-    return bool(_lib.load().tmgcn_wdgcn_supported(F0, H))
+@functools.lru_cache(maxsize=None)          # a shape's answer never changes (1-2 us per ctypes call)
+def _widths_ok(symbol: str, a: int, b: int) -> bool:
+    return bool(getattr(_lib.load(), symbol)(a, b))
+
+
+def _route(narrow_ok: bool, wide_ok: bool) -> str:
+    return "narrow" if narrow_ok else "wide" if wide_ok else "torch"
 
 
 def wdgcn_supported(F0: int, H: int) -> bool:
     """True when the narrow fused WD-GCN kernels (csrc/wdgcn.hip) cover the widths: 1 <= F0 <= 8, 1 <= H <= 8."""
-    return kernels.name == "hip" and _wdgcn_widths_ok(int(F0), int(H))
-
-
-@functools.lru_cache(maxsize=None)
-def _wdgcn_wide_widths_ok(F0: int, H: int) -> bool:
-    return bool(_lib.load().tmgcn_wdgcn_wide_supported(F0, H))
+    return kernels.name == "hip" and _widths_ok("tmgcn_wdgcn_supported", int(F0), int(H))
 
 
 def wdgcn_wide_supported(F0: int, H: int) -> bool:
     """True when the wide WD-GCN kernels (csrc/wdgcn_wide.hip, exact-f32 MFMA) cover the widths: 1 <= F0 <= 64,
     1 <= H <= 64 and not both <= 8 (those belong to the narrow kernels)."""
-    return kernels.name == "hip" and _wdgcn_wide_widths_ok(int(F0), int(H))
+    return kernels.name == "hip" and _widths_ok("tmgcn_wdgcn_wide_supported", int(F0), int(H))
 
 
 def wdgcn_lstm_route(F0: int, H: int) -> str:
     """Which implementation ops.wdgcn_lstm runs at these widths: "narrow" (csrc/wdgcn.hip), "wide"
     (csrc/wdgcn_wide.hip) or "torch" (wdgcn_lstm_torch: widths beyond 64)."""
-    if wdgcn_supported(F0, H):
-        return "narrow"
-    if wdgcn_wide_supported(F0, H):
-        return "wide"
-    return "torch"
+    return _route(wdgcn_supported(F0, H), wdgcn_wide_supported(F0, H))
 
 
 def wdgcn_lstm_torch(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tensor) -> torch.Tensor:
@@ -776,35 +771,21 @@ def wdgcn_lstm(AX: torch.Tensor, params, h0: torch.Tensor, c0: torch.Tensor, T_r
 EGCN_GATE_NAMES = ("W_Z", "U_Z", "B_Z", "W_R", "U_R", "B_R", "W_H", "U_H", "B_H")    # ef:38-46, in order
 
 
-@functools.lru_cache(maxsize=None)
-def _egcn_widths_ok(F: int, k: int) -> bool:
-    return bool(_lib.load().tmgcn_egcn_supported(F, k))
-
-
 def egcn_supported(F: int, k: int) -> bool:
     """True when the EvolveGCN-H kernels (csrc/evolvegcn.hip) cover the widths: 1 <= F <= 8, 1 <= k <= 8."""
-    return kernels.name == "hip" and _egcn_widths_ok(int(F), int(k))
-
-
-@functools.lru_cache(maxsize=None)
-def _egcn_wide_widths_ok(F: int, k: int) -> bool:
-    return bool(_lib.load().tmgcn_egcn_wide_supported(F, k))
+    return kernels.name == "hip" and _widths_ok("tmgcn_egcn_supported", int(F), int(k))
 
 
 def egcn_wide_supported(F: int, k: int) -> bool:
     """True when the wide EvolveGCN-H kernels (csrc/evolvegcn_wide.hip, fp64) cover the widths: 1 <= F <= 64,
     1 <= k <= 64 and not both <= 8 (those belong to the narrow kernels)."""
-    return kernels.name == "hip" and _egcn_wide_widths_ok(int(F), int(k))
+    return kernels.name == "hip" and _widths_ok("tmgcn_egcn_wide_supported", int(F), int(k))
 
 
 def egcn_evolve_route(F: int, k: int) -> str:
     """Which implementation ops.egcn_evolve runs at these widths: "narrow" (csrc/evolvegcn.hip), "wide"
     (csrc/evolvegcn_wide.hip) or "torch" (egcn_evolve_torch: widths beyond 64)."""
-    if egcn_supported(F, k):
-        return "narrow"
-    if egcn_wide_supported(F, k):
-        return "wide"
-    return "torch"
+    return _route(egcn_supported(F, k), egcn_wide_supported(F, k))
 
 
 def egcn_evolve_torch(H: torch.Tensor, p: torch.Tensor, gates, W_init: torch.Tensor, T_run: Optional[int] = None):
