@@ -214,6 +214,20 @@ __device__ __forceinline__ void quad_transpose4(float (&v)[4], int j) {
   }
 }
 
+__device__ __forceinline__ int64_t readlane64(int64_t v, int l) {   // l wave-uniform
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v & 0xffffffff), l);
+  const int hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
+  return ((int64_t)hi << 32) | lo;
+}
+
+template <int N, typename T>
+__device__ __forceinline__ T pick(const T (&v)[N], int i) {   // v[i] for a lane-dependent i: compare chain, no scratch
+  T r = v[0];
+#pragma unroll
+  for (int q = 1; q < N; ++q) r = (i == q) ? v[q] : r;
+  return r;
+}
+
 // Σ over the 64 lanes of a wave, the same value in every lane, without the LDS crossbar: four DPP steps inside each row of
 // 16 lanes (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror), then the four rows' sums read as scalars and added
 // in row order.  A fixed order (reproducible); 11 VALU operations where a __shfl_xor butterfly is six ds_bpermute round trips.

@@ -833,9 +833,6 @@ __device__ __forceinline__ void split3(float a, float b, unsigned& h, unsigned& 
 #ifndef X3_FLUSH
 #define X3_FLUSH 4
 #endif
-#ifndef X3_SCHED
-#define X3_SCHED 1
-#endif
 // (The same products on v_mfma_f32_16x16x32_bf16 — 16 tiles of 16x16 per wave and step — were measured in round 3: the same
 // time within 2 %, a higher clock at twice the MFMA count; profiles/archive/r3c_ab_dw_m16.txt.  Not kept.)
 constexpr int X3_ROWS = 32;
@@ -961,7 +958,6 @@ __global__ __launch_bounds__(256, X3_OCC) void gemm_dw_bf16x3_kernel(DwArgs a) {
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t], 0, 0, 0);
       }
     }
-#if X3_SCHED
     // Software-pipeline the LDS fragment reads against the MFMAs (left to itself hipcc issues each
     // group's ds_read_b128s right in front of the MFMA that needs them and waits out their latency,
     // 8-10 times per step): A fragments of half 0 + B fragments of group 0 first, then every group of
@@ -980,7 +976,6 @@ __global__ __launch_bounds__(256, X3_OCC) void gemm_dw_bf16x3_kernel(DwArgs a) {
     X3_SGB_MFMAS(6);                   //        group 7
 #undef X3_SGB_READS
 #undef X3_SGB_MFMAS
-#endif
     if (++since_flush == X3_FLUSH) flush();
   };
 

@@ -70,14 +70,6 @@ struct HeadLossArgs {
   float* pW;
 };
 
-template <int N, typename T>
-__device__ __forceinline__ T pick(const T (&v)[N], int i) {   // v[i] for a lane-dependent i: compare chain, no scratch
-  T r = v[0];
-#pragma unroll
-  for (int q = 1; q < N; ++q) r = (i == q) ? v[q] : r;
-  return r;
-}
-
 template <int N>
 __device__ __forceinline__ void load_in(const float* __restrict__ base, int64_t r, float (&v)[N]) {
   const float2* p = reinterpret_cast<const float2*>(base + r * N);

@@ -59,20 +59,6 @@ struct L12Args {
   int32_t n_blk;
 };
 
-__device__ __forceinline__ int64_t l12_readlane64(int64_t v, int l) {   // l wave-uniform
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v & 0xffffffff), l);
-  const int hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
-  return ((int64_t)hi << 32) | lo;
-}
-
-template <int N, typename T>
-__device__ __forceinline__ T pick_at(const T (&v)[N], int i) {
-  T r = v[0];
-#pragma unroll
-  for (int q = 1; q < N; ++q) r = (i == q) ? v[q] : r;
-  return r;
-}
-
 // NB consecutive non-zeros starting at `base`, as unaligned 16-byte loads (four column indices / four values each) while they
 // lie inside the arrays, element loads clamped to the last entry otherwise (the tail of the last rows only).  Every load
 // is unconditional and every column index returned is a valid one: the caller skips the positions past its row's end.
@@ -244,7 +230,7 @@ __global__ __launch_bounds__(256) void l12_fwd_kernel(L12Args a) {
 #pragma unroll
       for (int f = 0; f < F; ++f) acc[f] += __shfl_xor(acc[f], o);
     if (a.AX) {
-      for (int f = gl; f < F; f += G) a.AX[r * F + f] = pick_at<F>(acc, f);
+      for (int f = gl; f < F; f += G) a.AX[r * F + f] = pick<F>(acc, f);
     }
     for (int n = gl; n < NT; n += G) {
       float s = 0.f;
@@ -611,7 +597,7 @@ __global__ __launch_bounds__(256) void l12_bwd_kernel(L12Args a) {
       const int lane = threadIdx.x & 63;
       for (uint64_t m = __ballot(is_long && gl == 0); m; m &= m - 1) {
         const int src = __builtin_ctzll(m);
-        const int64_t r2 = l12_readlane64(r, src), b2 = l12_readlane64(beg, src), e2 = l12_readlane64(end, src);
+        const int64_t r2 = readlane64(r, src), b2 = readlane64(beg, src), e2 = readlane64(end, src);
         const int64_t xoff2 = (r2 / a.N) * (int64_t)a.N;
         float tw[NT];
 #pragma unroll
@@ -673,7 +659,7 @@ __global__ __launch_bounds__(256) void l12_bwd_kernel(L12Args a) {
       const int q = gl + j * G;
       if (q < NO) {
         const int k = q / F, f = q - k * F;
-        acc[j] = fma((double)pick_at<KI>(h, k), (double)pick_at<F>(dP, f), acc[j]);
+        acc[j] = fma((double)pick<KI>(h, k), (double)pick<F>(dP, f), acc[j]);
       }
     }
   }

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void spmm_vec4_kernel(
     if (r_begin + kTileRows < r_end) r_end = r_begin + kTileRows;
     TileRows rows;
     rows.load(rowptr, r_begin, r_end, lane);
-    if (TMGCN_HEAVY_FIRST && !scanning && rows.entries > heavy.thr) continue;   // done in somebody's pass 1
+    if (!scanning && rows.entries > heavy.thr) continue;   // done in somebody's pass 1
     // a tile of few entries is walked entry-major, several rows per wave at once (spmm_row.h "Short tiles")
     const int n_tile_rows = (int)(r_end - r_begin);
     if (short_tile(rows, true)) {

@@ -26,12 +26,26 @@ namespace tmgcn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// tuning knobs (defaults = the measured best; tools/ab_variants.sh builds alternatives)
+// Numeric tunables: each feeds a template argument or a constant and guards no alternative code.  The defaults are the
+// measured best; tools/ab_variants.sh builds other values.  (The alternatives that were measured and rejected are patches
+// under profiles/r6/not_kept/, not switches in this file.)
 #ifndef TMGCN_FUSED_OCC
 #define TMGCN_FUSED_OCC 4   // min waves per SIMD asked of the register allocator (A/B: 4 beats 3 by 4.5 %)
 #endif
 #ifndef TMGCN_FUSED_U
 #define TMGCN_FUSED_U 4     // gathers in flight per lane (F = 64 / 128 variants)
+#endif
+#ifndef TMGCN_FUSED_US
+#define TMGCN_FUSED_US 1    // gathers in flight per lane on short tiles, as a multiple of U
+#endif
+#ifndef TMGCN_FUSED_MFMA_PRIO
+#define TMGCN_FUSED_MFMA_PRIO 3  // issue priority of the product phase (both kernels)
+#endif
+#ifndef TMGCN_BX3_US
+#define TMGCN_BX3_US 4           // the bf16-product kernel: gathers in flight per lane on its short tiles
+#endif
+#ifndef TMGCN_BX3_MAX_DEG
+#define TMGCN_BX3_MAX_DEG 14     // launches with fewer entries per row (the caller's hint) take the bf16-product kernel (measured against the tile kernel: -9 % at 4, -6 % at 8, -4 % at 12; at 33 = S4 it would be 2 % faster too, but the adjoint identity at S4 size then holds to 4-7e-5 instead of 1e-5: the headline stays on the exact-f32 chain; profiles/r6/r6_44_*, not_kept/r6_73_*, not_kept/r6_74_*)
 #endif
 
 constexpr int FBM = 64;         // rows per tile
@@ -60,31 +74,6 @@ struct FusedArgs {
   unsigned int* tile_counter;  // dynamic tile scheduling (common.h): two counters, [0] tiles, [1] scan windows (spmm_row.h)
   GiantPlan giant;             // rows summed chunk by chunk in front of this launch (spmm_row.h), or rows == nullptr
 };
-
-#ifndef TMGCN_FUSED_US
-#define TMGCN_FUSED_US 1    // gathers in flight per lane on short tiles, as a multiple of U
-#endif
-#ifndef TMGCN_BX3_US
-#define TMGCN_BX3_US 4           // gathers in flight per lane on its short tiles
-#endif
-#ifndef TMGCN_BX_STAGED_Y
-#define TMGCN_BX_STAGED_Y 1      // the bf16-product kernel's Y tile leaves through LDS as whole rows (0: 64-byte pieces from the accumulators)
-#endif
-#ifndef TMGCN_BX_DRAW_AHEAD
-#define TMGCN_BX_DRAW_AHEAD 1
-#endif
-#ifndef TMGCN_BX3_MAX_DEG
-#define TMGCN_BX3_MAX_DEG 14     // launches with fewer entries per row (the caller's hint) take the bf16-product kernel (measured against the tile kernel: -9 % at 4, -6 % at 8, -4 % at 12; at 33 = S4 it would be 2 % faster too, but the adjoint identity at S4 size then holds to 4-7e-5 instead of 1e-5: the headline stays on the exact-f32 chain; profiles/r6/r6_44_*, not_kept/r6_73_*, not_kept/r6_74_*)
-#endif
-#ifndef TMGCN_FUSED_MFMA_PRIO
-#define TMGCN_FUSED_MFMA_PRIO 3
-#endif
-#ifndef TMGCN_FUSED_BLOCKS
-#define TMGCN_FUSED_BLOCKS 4   // development only: resident blocks per CU the grid is sized for (of 4)
-#endif
-#ifndef TMGCN_DEV_SKIP
-#define TMGCN_DEV_SKIP 0    // development only (phase breakdown, profiles/r6/r6_05_*): 1 no gather, 2 no products, 4 no Y stores, 8 a third of the products
-#endif
 
 // Development build only (-DTMGCN_FUSED_TRACE, tools/fused_trace.py): thread 0 of every block sums the 100 MHz wall-clock time
 // it spends in each phase of its tiles — separately for short tiles (entry-major walk) and the others — and leaves the
@@ -128,7 +117,6 @@ __device__ __forceinline__ void fused_gather_tile(const FusedArgs& a, float* As,
   const int n_tile_rows = row_end - row0 < FBM ? (int)(row_end - row0) : FBM;
   const int64_t slice0 = row0 / a.N;
   const bool is_short = short_tile(rows, row0 + n_tile_rows <= (slice0 + 1) * a.N);
-  if (TMGCN_DEV_SKIP & 1) return;
   if (is_short) {
     gather_short_tile<LPR, US>(a.col, a.val, a.X + slice0 * (int64_t)a.N * F4, rows, n_tile_rows, F4, lane, wave, F4,
                                [&](int rr, const float4& acc, int fl) {
@@ -189,7 +177,6 @@ __device__ __forceinline__ void fused_store_half(const f32x16& acc, const ActApp
   for (int i = 0; i < 16; ++i) {
     const int k = (i & 3) + 8 * (i >> 2);
     const float s = acc[i];
-    if ((TMGCN_DEV_SKIP & 4) && s != 12345.f) continue;
     if (GUARD && k >= rows_left) continue;
     if (PRE) store_f1(&Pb[k * Nf + lane_off], s);
     store_f1(&Yb[k * Nf + lane_off], ACT ? act(s) : s);
@@ -217,7 +204,7 @@ __device__ __forceinline__ void fused_store_half(const f32x16& acc, int act_id, 
 template <int NJ>
 __device__ __forceinline__ void fused_mfma_tile(const FusedArgs& a, const float* As, const float (&wreg)[NJ][4], int64_t row0,
                                                 int64_t row_end, int n0, int li, int lh) {
-  if (n0 >= a.Nf || (TMGCN_DEV_SKIP & 2)) return;
+  if (n0 >= a.Nf) return;
   const float* Arow = &As[li * FLDA + 4 * lh];
   const int n = n0 + li;
 #pragma unroll
@@ -227,7 +214,7 @@ __device__ __forceinline__ void fused_mfma_tile(const FusedArgs& a, const float*
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     float4 av_next = *reinterpret_cast<const float4*>(Arow + mb * 32 * FLDA);
 #pragma unroll
-    for (int j = 0; j < ((TMGCN_DEV_SKIP & 8) ? (NJ + 2) / 3 : NJ); ++j) {      // (8: a THIRD of the products — a timing bound, wrong results)
+    for (int j = 0; j < NJ; ++j) {
       const float4 av = av_next;
       if (j + 1 < NJ) av_next = *reinterpret_cast<const float4*>(Arow + mb * 32 * FLDA + 8 * (j + 1));
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wreg[j][0], acc, 0, 0, 0);
@@ -297,8 +284,8 @@ __global__ __launch_bounds__(256, TMGCN_FUSED_OCC) void spmm_gemm_kernel(FusedAr
     FT_STAMP(ft_b);
     TileRows rows;
     rows.load(a.rowptr, row0, row_end, lane);
-    if (TMGCN_HEAVY_FIRST && !scanning && rows.entries > heavy.thr) {   // done in somebody's pass 1
-      __syncthreads();                                                 // (s_tile is rewritten at the top)
+    if (!scanning && rows.entries > heavy.thr) {   // done in somebody's pass 1
+      __syncthreads();                             // (s_tile is rewritten at the top)
       continue;
     }
     FT_WAIT();
@@ -399,7 +386,7 @@ __global__ __launch_bounds__(512, 4) void spmm_gemm_bx3_kernel(FusedArgs a) {
   int64_t cur_batch = -1;
   if (threadIdx.x == 0) s_row = 8;
   // whole rows of aligned float4: Y leaves through LDS (see the epilogue)
-  const bool staged = TMGCN_BX_STAGED_Y && a.Nf % 4 == 0 && reinterpret_cast<uintptr_t>(a.Y) % 16 == 0 && reinterpret_cast<uintptr_t>(a.pre) % 16 == 0;
+  const bool staged = a.Nf % 4 == 0 && reinterpret_cast<uintptr_t>(a.Y) % 16 == 0 && reinterpret_cast<uintptr_t>(a.pre) % 16 == 0;
   HeavyScan heavy;                                                         // the heaviest tiles first, as in the tile kernel
   heavy.init(a.rowptr, tm);
   bool have_next = false;                                                  // s_tile holds the main loop's next tile
@@ -423,7 +410,7 @@ __global__ __launch_bounds__(512, 4) void spmm_gemm_bx3_kernel(FusedArgs a) {
     const int64_t batch = a.rows_per_batch ? row0 / a.rows_per_batch : 0;
     TileRows rows;
     rows.load(a.rowptr, row0, row_end, lane);
-    if (TMGCN_HEAVY_FIRST && !scanning && rows.entries > heavy.thr) {     // done in somebody's pass 1
+    if (!scanning && rows.entries > heavy.thr) {                           // done in somebody's pass 1
       __syncthreads();
       continue;
     }
@@ -490,7 +477,7 @@ __global__ __launch_bounds__(512, 4) void spmm_gemm_bx3_kernel(FusedArgs a) {
     if (threadIdx.x == 0) s_row = 8;
     // the main loop's next tile is drawn now, under the products (one barrier and the draw's round trip less per tile)
     unsigned int drawn = 0;
-    if (TMGCN_BX_DRAW_AHEAD && !scanning && threadIdx.x == 0) drawn = atomicAdd(a.tile_counter, 1u);
+    if (!scanning && threadIdx.x == 0) drawn = atomicAdd(a.tile_counter, 1u);
     // ---- products: 4 row blocks of 16 x this wave's 16 columns; per (row block, k-step) six plane products, small terms first
     __builtin_amdgcn_s_setprio(TMGCN_FUSED_MFMA_PRIO);
     int lane_p = lane0;
@@ -525,29 +512,7 @@ __global__ __launch_bounds__(512, 4) void spmm_gemm_bx3_kernel(FusedArgs a) {
     }
     __builtin_amdgcn_s_setprio(0);
     // epilogue: accumulator i of block rb is row 16 rb + 4 lg + i, column n0 + lm
-    if (TMGCN_BX_STAGED_Y == 2 && staged) {
-      // development (measured: the same time as the dword stores, profiles/r6/r6_82_*): no LDS, no barrier — the 4 x 4 blocks
-      // transposed on the lane quads (common.h), 16 bytes per lane: a quarter of the store instructions, every row still leaving as
-      // 64-byte pieces.  It is the pieces that cost, not the instruction count.
-      const int j = lm & 3, cq = n0 + 4 * (lm >> 2);
-      if (cq < a.Nf) {
-        const ActApply act(a.act);
-        float* __restrict__ Yb = a.Y + row0 * a.Nf;
-        float* __restrict__ Pb = a.pre ? a.pre + row0 * a.Nf : nullptr;
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-          float v[4] = {acc[rb][0], acc[rb][1], acc[rb][2], acc[rb][3]};
-          quad_transpose4(v, j);
-          const int rr = 16 * rb + 4 * lg + j;
-          if (rr < n_tile_rows) {
-            float4 q = make_float4(v[0], v[1], v[2], v[3]);
-            if (Pb) store_f4(reinterpret_cast<float4*>(&Pb[rr * a.Nf + cq]), q);
-            if (a.act != TMGCN_ACT_NONE) q = make_float4(act(q.x), act(q.y), act(q.z), act(q.w));
-            store_f4(reinterpret_cast<float4*>(&Yb[rr * a.Nf + cq]), q);
-          }
-        }
-      }
-    } else if (!staged) {                                                // (an output that is not a whole number of aligned float4 per row)
+    if (!staged) {                                                       // (an output that is not a whole number of aligned float4 per row)
       const int n = n0 + lm;
       if (n < a.Nf) {
         const ActApply act(a.act);
@@ -590,7 +555,6 @@ __global__ __launch_bounds__(512, 4) void spmm_gemm_bx3_kernel(FusedArgs a) {
           const int rr = 16 * k + 2 * wave + (lane_s >> 5);
           if (rr < n_tile_rows) {
             float4 v = *reinterpret_cast<const float4*>(&yt[rr * BX_YPITCH + 4 * c4]);
-            if (TMGCN_DEV_SKIP & 4) continue;
             if (Pb) store_f4(reinterpret_cast<float4*>(&Pb[rr * a.Nf + 4 * c4]), v);
             if (a.act != TMGCN_ACT_NONE) v = make_float4(act(v.x), act(v.y), act(v.z), act(v.w));
             store_f4(reinterpret_cast<float4*>(&Yb[rr * a.Nf + 4 * c4]), v);
@@ -598,7 +562,7 @@ __global__ __launch_bounds__(512, 4) void spmm_gemm_bx3_kernel(FusedArgs a) {
         }
       }
     }
-    if (TMGCN_BX_DRAW_AHEAD && !scanning) {
+    if (!scanning) {
       if (threadIdx.x == 0) s_tile = drawn;                                // (everybody read the current tile's number before the barrier behind the gather)
       have_next = true;
     }
@@ -773,7 +737,6 @@ extern "C" int tmgcn_spmm_gemm_f32_plan(const int64_t* rowptr, const int32_t* co
 #define TMGCN_FUSED_CASE(KK, L, UU)                                                              \
   case KK: {                                                                                     \
     int64_t gx = persistent_grid_reserved(spmm_gemm_kernel<L, UU, KK / 8>, 256, grid_reserve);                 \
-    gx = gx * TMGCN_FUSED_BLOCKS / 4;                                                            \
     if (gx > a.n_tiles) gx = a.n_tiles;                                                          \
     hipLaunchKernelGGL((spmm_gemm_kernel<L, UU, KK / 8>), dim3((unsigned)gx), dim3(256), 0, st, a); \
     break;                                                                                       \

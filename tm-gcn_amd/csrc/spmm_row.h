@@ -87,18 +87,9 @@ __device__ __forceinline__ float4 gather_row(const int32_t* __restrict__ col,
 #ifndef TMGCN_LONG_ROW
 #define TMGCN_LONG_ROW 256
 #endif
-#ifndef TMGCN_HEAVY_FIRST
-#define TMGCN_HEAVY_FIRST 1
-#endif
 constexpr int kTileRows = 64;                 // rows per tile of both kernels
 constexpr int kLongRow = TMGCN_LONG_ROW;
 constexpr int64_t kHeavyMin = 8192;
-
-__device__ __forceinline__ int64_t readlane64(int64_t v, int l) {   // l wave-uniform
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v & 0xffffffff), l);
-  const int hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
-  return ((int64_t)hi << 32) | lo;
-}
 
 // tile -> rows.  Tiles restart at every UNIT of rows — a slice (N rows) in every launch the layers make — in the plain and in
 // the fused kernel alike: a tile never straddles two slices, and a row falls into the same tile whichever kernel, weight
@@ -133,7 +124,7 @@ struct HeavyScan {
     thr = 8 * mean > kHeavyMin ? 8 * mean : kHeavyMin;
     win = 0;
     pending = 0;
-    scanning = TMGCN_HEAVY_FIRST != 0;
+    scanning = true;
   }
   // next heavy tile of this block, or -1 when the scan is over (then `scanning` is false); s_slot: one LDS word of the block
   __device__ __forceinline__ int64_t next(const int64_t* __restrict__ rowptr, const TileMap& m, unsigned int* scan_counter,

@@ -15,7 +15,6 @@ product never does).
 from __future__ import annotations
 
 import functools
-import os
 
 import ctypes as C
 from typing import Optional
@@ -566,11 +565,6 @@ def layer12_supported(K0: int, F: int, Nf: int) -> bool:
     return kernels.name == "hip" and _layer12_widths_ok(int(K0), int(F), int(Nf))
 
 
-# A/B switch of the entry-balanced row blocks of the entry-major layer kernels (tools/: TMGCN_L12_ROW_BLOCKS=0 gives the
-# kernels' own 256-row blocks; the forward's results do not depend on it, the backward's dW1 to fp32 summation order)
-L12_ROW_BLOCKS = os.environ.get("TMGCN_L12_ROW_BLOCKS", "1") != "0"
-
-
 def layer12(H: torch.Tensor, W1: torch.Tensor, act1, A: BatchedCSR, W2: torch.Tensor, act2=None, fuse: Optional[bool] = None):
     """act2((Â ⋆ act1(H·W1))·W2): layers 1 and 2 of the narrow 2-layer models (ehf:330-335 + 348-349; 486-487) with H the
     model's cached constant (AtXt / AX).  One forward and one backward launch (csrc/layer12.hip) when H carries no
@@ -587,9 +581,9 @@ def layer12(H: torch.Tensor, W1: torch.Tensor, act1, A: BatchedCSR, W2: torch.Te
         return spmm_feature_gemm(A, feature_gemm(H, W1, act=act1), W2, act=act2)
     need = torch.is_grad_enabled() and W1.requires_grad
     # row blocks cut by entries where 256-row blocks would hold several tiles (real, skewed data): csr.BatchedCSR.row_blocks
-    blk = A.row_blocks() if (A.N >= 256 and L12_ROW_BLOCKS) else None
+    blk = A.row_blocks() if A.N >= 256 else None
     t_blk = None
-    if need and A.N >= 256 and L12_ROW_BLOCKS:
+    if need and A.N >= 256:
         # the backward takes its entry-major kernel whenever it is handed a partition (include/tmgcn.h): sparse rows take that
         # kernel anyway, skewed ones (hub rows) are 1.7x faster on it, evenly filled denser ones are not — no partition there.
         At = A.transpose()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The narrow SpMM kernels (F <= 8: G lanes per row) on a graph with one hub row, this tree against a library variant built
-from an earlier commit (tools/ab_r4_baseline.sh REV prev): T = 32 slices of N = 20 000 nodes, 17 entries per row, F = 6,
+"""The narrow SpMM kernels (F <= 8: G lanes per row) on a graph with one hub row, this tree against a library variant
+(build/variants/NAME/libtmgcn_hip.so, e.g. the kernels of an earlier commit built there): T = 32 slices of N = 20 000 nodes, 17 entries per row, F = 6,
 one row replaced by a hub of H entries.   python tools/narrow_hub_probe.py [variant]"""
 import ctypes as C
 import os
