@@ -196,6 +196,28 @@ int tmgcn_spmm_gemm_f32_plan(const int64_t* rowptr, const int32_t* col, const fl
                              int32_t n_giant, int32_t n_giant_chunks, float* giant_ws, int64_t giant_ws_bytes,
                              void* stream);
 
+/* ---- P2+P3 fused, the gathered operand STORED in bf16 -------------------------------
+ * The same contraction as tmgcn_spmm_gemm_f32 — the pair  sparse.mm loop + t.matmul(AtXt, W)  (ehf:206-207 + 222,
+ * 303-304 + 349, 471-472 + 486-489), and with the transposed CSR and trans_w=1 its backward pair — with X given as bf16
+ * bit patterns [n_rows][K]: the launch is bound by the bytes of the gathered rows, and these are 2·K instead of 4·K.
+ * Numerics: every gathered value is widened to fp32 (exact) and accumulated with fmaf against the fp32 val, a row's
+ * entries in a fixed order (no atomics: bit-reproducible from launch to launch); the products are the exact-f32 MFMA
+ * chain of tmgcn_spmm_gemm_f32; the result is what that entry point computes on the widened X, to fp32 summation order.
+ * AX (optional) and pre_act (optional) are fp32.  Y is fp32 (y_bf16 = 0) or bf16 (y_bf16 = 1: the post-activation fp32
+ * value rounded to nearest even once).  W, trans_w, rows_per_batch, w_batch_stride, act, grid_reserve as above;
+ * avg_nnz_per_row is accepted for symmetry and steers nothing.  Rows of any length are summed correctly (more than 256
+ * entries: by the four waves of a block); there is no giant-row plan.
+ * Supported when tmgcn_spmm_gemm_bf16_supported(K, Nf) != 0: K a multiple of 8 in [16, 128], 1 <= Nf <= 128.
+ * TMGCN_ERR_INVALID, and no launch, on unsupported widths, a NULL rowptr / X / W / Y, X / AX / Y not 16-byte aligned,
+ * or y_bf16 outside {0, 1}. */
+int tmgcn_spmm_gemm_bf16_supported(int32_t K, int32_t Nf);
+int tmgcn_spmm_gemm_bf16(const int64_t* rowptr, const int32_t* col, const float* val,
+                         const uint16_t* X_bf16, int64_t n_rows, int32_t N, int32_t K,
+                         const float* W, int32_t Nf, int32_t trans_w,
+                         int64_t rows_per_batch, int64_t w_batch_stride, int32_t act,
+                         void* Y, int32_t y_bf16, float* AX, float* pre_act, int32_t grid_reserve,
+                         float avg_nnz_per_row, void* stream);
+
 /* ---- P3: feature·weight contraction ----------------------------------------------
  * Replaces  t.matmul(AtXt, Wt)  ehf:222, 330, 340, 344, 349, 415, 486-489.
  *

@@ -21,25 +21,15 @@
 // products add up (DESIGN.md §4 "Short tiles").
 #include "common.h"
 #include "spmm_row.h"
+#include "spmm_gemm_tile.h"
 
 namespace tmgcn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Numeric tunables: each feeds a template argument or a constant and guards no alternative code.  The defaults are the
 // measured best; tools/ab_variants.sh builds other values.  (The alternatives that were measured and rejected are patches
 // under profiles/r6/not_kept/, not switches in this file.)
-#ifndef TMGCN_FUSED_OCC
-#define TMGCN_FUSED_OCC 4   // min waves per SIMD asked of the register allocator (A/B: 4 beats 3 by 4.5 %)
-#endif
-#ifndef TMGCN_FUSED_U
-#define TMGCN_FUSED_U 4     // gathers in flight per lane (F = 64 / 128 variants)
-#endif
 #ifndef TMGCN_FUSED_US
 #define TMGCN_FUSED_US 1    // gathers in flight per lane on short tiles, as a multiple of U
-#endif
-#ifndef TMGCN_FUSED_MFMA_PRIO
-#define TMGCN_FUSED_MFMA_PRIO 3  // issue priority of the product phase (both kernels)
 #endif
 #ifndef TMGCN_BX3_US
 #define TMGCN_BX3_US 4           // the bf16-product kernel: gathers in flight per lane on its short tiles
@@ -47,10 +37,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifndef TMGCN_BX3_MAX_DEG
 #define TMGCN_BX3_MAX_DEG 14     // launches with fewer entries per row (the caller's hint) take the bf16-product kernel (measured against the tile kernel: -9 % at 4, -6 % at 8, -4 % at 12; at 33 = S4 it would be 2 % faster too, but the adjoint identity at S4 size then holds to 4-7e-5 instead of 1e-5: the headline stays on the exact-f32 chain; profiles/r6/r6_44_*, not_kept/r6_73_*, not_kept/r6_74_*)
 #endif
-
-constexpr int FBM = 64;         // rows per tile
-constexpr int FKC = 128;        // max K (feature width of X)
-constexpr int FLDA = FKC + 4;   // LDS row stride in floats
 
 struct FusedArgs {
   const int64_t* rowptr;
@@ -88,24 +74,7 @@ __device__ unsigned long long fused_trace_words[4096 * 16];
 #define FT_WAIT() do { } while (0)
 #endif
 
-// ---- the three pieces of the fused kernel ----------------------------------------------------------------------------
-
-// W fragments of a wave's 32-column strip (n0 .. n0+31): B operand of v_mfma_f32_32x32x2_f32, k = 8j + s + 4·lh
-template <int NJ>
-__device__ __forceinline__ void fused_load_w(const FusedArgs& a, int64_t batch, int n0, int li, int lh, float (&wreg)[NJ][4]) {
-  const float* Wb = a.W + (a.rows_per_batch ? batch * a.w_batch_stride : 0);
-  const int n = n0 + li;
-  const int nc = n < a.Nf ? n : 0;  // clamp: out-of-range columns load column 0, zeroed below
-  const float* Wl = a.trans_w ? Wb + (int64_t)nc * a.K + 4 * lh : Wb + (int64_t)(4 * lh) * a.Nf + nc;
-  const int64_t sk = a.trans_w ? 1 : a.Nf;  // stride of k
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const float w = Wl[(int64_t)(8 * j + s) * sk];
-      wreg[j][s] = n < a.Nf ? w : 0.f;
-    }
-}
+// ---- the gather of the fused kernel (its W fragments and product phase: spmm_gemm_tile.h) ----------------------------------------------------------------------------
 
 // Phase 1: the row sums of one tile into the LDS tile `As` ([64][FLDA]) and, when asked for, to AX; all four waves.
 // A tile of few entries entry-major, several rows per wave at once (spmm_row.h "Short tiles"); otherwise 16 rows per wave,
@@ -165,76 +134,6 @@ __device__ __forceinline__ void fused_gather_tile(const FusedArgs& a, float* As,
     if (wave == (rr & 3) && lane < LPR && lane < F4) {
       *reinterpret_cast<float4*>(&As[rr * FLDA + 4 * lane]) = acc;
       if (a.AX) store_f4(&reinterpret_cast<float4*>(a.AX)[r * F4 + lane], acc);
-    }
-  }
-}
-
-// The 16 accumulators of a lane after a 32-row half: accumulator i is row k(i) + 4·lh of the half, k(i) = (i & 3) + 8·(i >> 2).
-template <bool GUARD, bool PRE, bool ACT>
-__device__ __forceinline__ void fused_store_half(const f32x16& acc, const ActApply& act, float* __restrict__ Yb, float* __restrict__ Pb,
-                                                 int Nf, int lane_off, int rows_left) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int k = (i & 3) + 8 * (i >> 2);
-    const float s = acc[i];
-    if (GUARD && k >= rows_left) continue;
-    if (PRE) store_f1(&Pb[k * Nf + lane_off], s);
-    store_f1(&Yb[k * Nf + lane_off], ACT ? act(s) : s);
-  }
-}
-template <bool GUARD>
-__device__ __forceinline__ void fused_store_half(const f32x16& acc, int act_id, float* __restrict__ Yb, float* __restrict__ Pb, int Nf,
-                                                 int lane_off, int rows_left) {
-  const ActApply act(act_id);             // decoded once (the same bits as act_apply); no activation: the raw sums, no select chain
-  if (act_id == TMGCN_ACT_NONE) {
-    if (Pb) fused_store_half<GUARD, true, false>(acc, act, Yb, Pb, Nf, lane_off, rows_left);
-    else fused_store_half<GUARD, false, false>(acc, act, Yb, Pb, Nf, lane_off, rows_left);
-  } else {
-    if (Pb) fused_store_half<GUARD, true, true>(acc, act, Yb, Pb, Nf, lane_off, rows_left);
-    else fused_store_half<GUARD, false, true>(acc, act, Yb, Pb, Nf, lane_off, rows_left);
-  }
-}
-
-// Phase 2: tile · Wop on the matrix cores, the wave's 32 output columns [n0, n0 + 32).
-// One 32-row half of the tile at a time: its 16 accumulators are stored before the other half's products
-// start, so only ONE accumulator set is live next to the 64 W-fragment registers (both halves live — the
-// round 1-3 form — cost 15 spilled VGPRs at 4 waves per SIMD; profiles/archive/r4*_ab_fused_spill.txt).
-// A fragments are fetched one k-group ahead of the MFMAs that use them; the sched_barrier keeps hipcc
-// from hoisting all the ds_read_b128 to the top.
-template <int NJ>
-__device__ __forceinline__ void fused_mfma_tile(const FusedArgs& a, const float* As, const float (&wreg)[NJ][4], int64_t row0,
-                                                int64_t row_end, int n0, int li, int lh) {
-  if (n0 >= a.Nf) return;
-  const float* Arow = &As[li * FLDA + 4 * lh];
-  const int n = n0 + li;
-#pragma unroll
-  for (int mb = 0; mb < FBM / 32; ++mb) {
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float4 av_next = *reinterpret_cast<const float4*>(Arow + mb * 32 * FLDA);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const float4 av = av_next;
-      if (j + 1 < NJ) av_next = *reinterpret_cast<const float4*>(Arow + mb * 32 * FLDA + 8 * (j + 1));
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wreg[j][0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, wreg[j][1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, wreg[j][2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, wreg[j][3], acc, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (n < a.Nf) {
-      // Epilogue: accumulator i of the lane is row rbase + k(i) + 4·lh, column n.  Everything but (4·lh)·Nf + n is uniform: the
-      // stores take a scalar base + a 32-bit lane offset, the activation is decoded once (ActApply: the same bits as
-      // act_apply; none at all for TMGCN_ACT_NONE), and a half tile that lies inside the slice skips the row guard.  (Round 6:
-      // a 64-bit address, a row compare and an activation switch per ELEMENT had made the epilogues a third of the product
-      // phase: 6.7 us per tile on an otherwise idle CU where the MFMAs need 3.6.)
-      const int64_t rbase = row0 + mb * 32;
-      float* __restrict__ Yb = a.Y + rbase * a.Nf;
-      float* __restrict__ Pb = a.pre ? a.pre + rbase * a.Nf : nullptr;
-      const int lane_off = (4 * lh) * a.Nf + n;
-      if (rbase + 32 <= row_end) fused_store_half<false>(acc, a.act, Yb, Pb, a.Nf, lane_off, 32);      // uniform: inside the slice
-      else fused_store_half<true>(acc, a.act, Yb, Pb, a.Nf, lane_off, (int)(row_end - rbase) - 4 * lh);  // rows k < rows_left exist
     }
   }
 }

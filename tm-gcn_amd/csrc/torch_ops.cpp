@@ -8,6 +8,7 @@
 //     tmgcn::mtransform          tmgcn_mtransform_f32              ehf:204, 308, 346, 404; Minv ehf:224
 //     tmgcn::spmm_csr_batched    tmgcn_spmm_csr_batched_f32_hint   ehf:206-207, 303-304, 310-311, 471-472
 //     tmgcn::spmm_gemm(_out)     tmgcn_spmm_gemm_f32               the two statements above + ehf:222 in one launch
+//     tmgcn::spmm_gemm_bf16      tmgcn_spmm_gemm_bf16              the same launch on an X stored in bf16
 //     tmgcn::bgemm               tmgcn_gemm_f32                    ehf:222, 330, 344, 349, 486-489
 //     tmgcn::bgemm_dW            tmgcn_gemm_dw_f32                 autograd of ehf:222
 //     tmgcn::edge_head_fwd/bwd   tmgcn_edge_head_*_f32             ehf:228-232, 351-355, 491-495
@@ -18,7 +19,7 @@
 //     tmgcn::egcn_fwd/bwd        tmgcn_egcn_fwd / _bwd             evolvegcn_functions.py:80-95 (EvolveGCN-H)
 //     tmgcn::egcn_wide_fwd/bwd   tmgcn_egcn_wide_fwd / _bwd        the same at widths up to 64
 //   differentiable ops (registered under the Autograd key)
-//     tmgcn::m_transform, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm,
+//     tmgcn::m_transform, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm(_bf16), tmgcn::round_bf16,
 //     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce, tmgcn::wdgcn_lstm, tmgcn::egcn_evolve, tmgcn::egcn_evolve_wide
 //
 // No kernels live here: every launch goes through the C-ABI shared library (libtmgcn_hip.so),
@@ -622,6 +623,45 @@ struct WidenFn : public torch::autograd::Function<WidenFn> {
 std::vector<Tensor> widen_params_ad(at::TensorList params) { return WidenFn::apply(params); }
 
 bool spmm_gemm_supported(int64_t K, int64_t Nf) { return tmgcn_spmm_gemm_supported((int32_t)K, (int32_t)Nf) != 0; }
+bool spmm_gemm_bf16_supported(int64_t K, int64_t Nf) { return tmgcn_spmm_gemm_bf16_supported((int32_t)K, (int32_t)Nf) != 0; }
+
+// The fused SpMM + GEMM on an operand STORED in bf16 (csrc/spmm_gemm_bf16.hip): X bf16 [T,N,K], W fp32; Y fp32 or bf16
+// (y_bf16), AX and pre fp32.  A 2-byte-aligned X that does not start on 16 bytes is copied once, as on the fp32 path.
+std::tuple<Tensor, Tensor, Tensor> spmm_gemm_bf16(const Tensor& rowptr, const Tensor& col, const Tensor& val, const Tensor& X,
+                                                  int64_t N, const Tensor& W, bool trans_w, int64_t act, bool want_ax,
+                                                  bool want_pre, bool y_bf16, int64_t grid_reserve, double avg_nnz_per_row) {
+  want(X, "spmm_gemm_bf16 X", at::kBFloat16);
+  want(W, "spmm_gemm_bf16 W");
+  check_csr(rowptr, col, val, X, N, "spmm_gemm_bf16");
+  c10::DeviceGuard g(X.device());
+  const WShape s = w_shape(W, trans_w, X.size(0), X.size(2), "spmm_gemm_bf16");
+  const auto f32 = X.options().dtype(at::kFloat);
+  Tensor Y = at::empty({X.size(0), N, s.wn}, y_bf16 ? X.options() : f32);
+  Tensor AX = want_ax ? at::empty(X.sizes(), f32) : Tensor();
+  Tensor pre = (want_pre && act != TMGCN_ACT_NONE) ? at::empty({X.size(0), N, s.wn}, f32) : Tensor();
+  const Tensor Xa = aligned16(X);
+  ok(tmgcn_spmm_gemm_bf16((const int64_t*)ptr(rowptr), (const int32_t*)ptr(col), (const float*)ptr(val),
+                          (const uint16_t*)ptr(Xa), X.size(0) * N, (int32_t)N, (int32_t)X.size(2), (const float*)ptr(W),
+                          (int32_t)s.wn, trans_w ? 1 : 0, s.per_slice ? N : 0, s.stride, (int32_t)act, ptr(Y), y_bf16 ? 1 : 0,
+                          (float*)ptr(AX), (float*)ptr(pre), (int32_t)grid_reserve, (float)avg_nnz_per_row, stream_of(X)),
+     "tmgcn_spmm_gemm_bf16");
+  return {Y, AX.defined() ? AX : none_like(W), pre.defined() ? pre : none_like(W)};
+}
+
+// fp32 -> bf16, rounded to nearest even once (one cast launch); backward: the gradient widened to fp32
+struct RoundBf16Fn : public torch::autograd::Function<RoundBf16Fn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& x) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    return cast_multi({x.contiguous()}, true)[0];
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    Tensor g = grads[0].contiguous();
+    if (g.scalar_type() == at::kBFloat16) g = cast_multi({g}, false)[0];
+    return {g};
+  }
+};
+
 bool layer12_supported(int64_t K0, int64_t F, int64_t Nf) { return tmgcn_layer12_supported((int32_t)K0, (int32_t)F, (int32_t)Nf) != 0; }
 // ---- WD-GCN (wd_gcn_functions.py:66-98): relu(AX·W) + the LSTM recurrence, and its BPTT ----------------------------
 // `wide` selects the kernels of csrc/wdgcn_wide.hip (widths up to 64) through tmgcn_wdgcn_wide_*: the same operator,
@@ -1037,6 +1077,61 @@ struct SpmmFeatureGemmFn : public torch::autograd::Function<SpmmFeatureGemmFn> {
   }
 };
 
+struct SpmmFeatureGemmBf16Fn : public torch::autograd::Function<SpmmFeatureGemmBf16Fn> {
+  // The fused P2+P3 on a bf16-stored X.  AX and pre are saved in fp32, so dW = AXᵀ·dY keeps the fp32 path's accuracy; the
+  // backward gather runs the same kernel on dY rounded to bf16 once, through the transposed CSR, and writes dX in bf16.
+  static Tensor forward(AutogradContext* ctx, const Tensor& X, const Tensor& W, const Tensor& rowptr, const Tensor& col,
+                        const Tensor& val, const OptTensor& t_rowptr, const OptTensor& t_col, const OptTensor& t_val, int64_t N,
+                        double avg, int64_t act, bool y_bf16, int64_t grid_reserve, bool need_x, bool need_w) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    auto [Y, AX, pre] = spmm_gemm_bf16(rowptr, col, val, X, N, W, false, act, need_w, need_x || need_w, y_bf16, grid_reserve, avg);
+    if (need_x)
+      TORCH_CHECK(t_rowptr.has_value() && t_col.has_value() && t_val.has_value(),
+                  "spmm_feature_gemm_bf16: X requires grad but no transposed adjacency was passed");
+    ctx->save_for_backward({W, AX, pre, need_x ? *t_rowptr : Tensor(), need_x ? *t_col : Tensor(), need_x ? *t_val : Tensor()});
+    ctx->saved_data["N"] = N;
+    ctx->saved_data["avg"] = avg;
+    ctx->saved_data["act"] = act;
+    ctx->saved_data["reserve"] = grid_reserve;
+    return Y;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    auto sv = ctx->get_saved_variables();
+    const Tensor &W = sv[0], &AX = sv[1], &pre = sv[2];
+    const int64_t N = ctx->saved_data["N"].toInt(), act = ctx->saved_data["act"].toInt();
+    const double avg = ctx->saved_data["avg"].toDouble();
+    Tensor dY = grads[0].contiguous(), dYb;                       // dYb: dY in bf16, rounded once
+    if (dY.scalar_type() == at::kBFloat16) {
+      if (act == TMGCN_ACT_NONE) dYb = dY;                        // (already rounded by whoever formed it)
+      dY = cast_multi({dY}, false)[0];
+    }
+    if (act != TMGCN_ACT_NONE) dY = act_bwd(pre, dY, act);        // the activation derivative in fp32
+    Tensor dX, dW;
+    if (ctx->needs_input_grad(0)) {
+      if (spmm_gemm_bf16_supported(dY.size(-1), W.size(-2))) {
+        if (!dYb.defined()) dYb = cast_multi({dY}, true)[0];
+        dX = std::get<0>(spmm_gemm_bf16(sv[3], sv[4], sv[5], dYb, N, W, true, TMGCN_ACT_NONE, false, false, true,
+                                        ctx->saved_data["reserve"].toInt(), avg));
+      } else {  // the transposed widths are outside the bf16 kernel's domain: the fp32 pair on the widened dY, rounded once
+        Tensor d32;
+        if (spmm_gemm_supported(dY.size(-1), W.size(-2)))
+          d32 = std::get<0>(spmm_gemm(sv[3], sv[4], sv[5], dY, N, W, true, TMGCN_ACT_NONE, false, false,
+                                      ctx->saved_data["reserve"].toInt(), avg, OptTensor(), OptTensor()));
+        else
+          d32 = spmm_csr_batched(sv[3], sv[4], sv[5], std::get<0>(bgemm(dY, W, true, TMGCN_ACT_NONE, false, TMGCN_GEMM_AUTO)), N, avg,
+                                 OptTensor(), OptTensor());
+        dX = cast_multi({d32}, true)[0];
+      }
+    }
+    if (ctx->needs_input_grad(1)) dW = bgemm_dW(AX, dY, W.dim() == 3, TMGCN_DW_AUTO);
+    variable_list out(15);
+    out[0] = dX;
+    out[1] = dW;
+    return out;
+  }
+};
+
 struct EdgeHeadFn : public torch::autograd::Function<EdgeHeadFn> {
   static Tensor forward(AutogradContext* ctx, const Tensor& Z, const Tensor& U, const Tensor& src, const Tensor& dst,
                         const OptTensor& eptr, const OptTensor& eidx, bool need) {
@@ -1365,6 +1460,14 @@ Tensor spmm_feature_gemm_ad(const Tensor& X, const Tensor& W, const Tensor& rowp
   return SpmmFeatureGemmFn::apply(X, W, rowptr, col, val, t_rowptr, t_col, t_val, N, avg, act, grid_reserve, g_rows, g_chunks,
                                   t_g_rows, t_g_chunks, grad && X.requires_grad(), grad && W.requires_grad());
 }
+Tensor spmm_feature_gemm_bf16_ad(const Tensor& X, const Tensor& W, const Tensor& rowptr, const Tensor& col, const Tensor& val,
+                                 const OptTensor& t_rowptr, const OptTensor& t_col, const OptTensor& t_val, int64_t N, double avg,
+                                 int64_t act, bool y_bf16, int64_t grid_reserve) {
+  const bool grad = at::GradMode::is_enabled();
+  return SpmmFeatureGemmBf16Fn::apply(X, W, rowptr, col, val, t_rowptr, t_col, t_val, N, avg, act, y_bf16, grid_reserve,
+                                      grad && X.requires_grad(), grad && W.requires_grad());
+}
+Tensor round_bf16_ad(const Tensor& x) { return RoundBf16Fn::apply(x); }
 Tensor edge_head_ad(const Tensor& Z, const Tensor& U, const Tensor& src, const Tensor& dst, const OptTensor& eptr,
                     const OptTensor& eidx) {
   return EdgeHeadFn::apply(Z, U, src, dst, eptr, eidx,
@@ -1450,6 +1553,9 @@ TORCH_LIBRARY(tmgcn, m) {
   m.def("spmm_gemm_out(Tensor rowptr, Tensor col, Tensor val, Tensor X, int N, Tensor W, bool trans_w, int act, "
         "Tensor(a!) Y, Tensor(b!)? AX, Tensor(c!)? pre, int grid_reserve, float avg_nnz_per_row=-1.0, Tensor? giant_rows=None, "
         "Tensor? giant_chunks=None) -> ()");
+  m.def("spmm_gemm_bf16(Tensor rowptr, Tensor col, Tensor val, Tensor X, int N, Tensor W, bool trans_w, int act, "
+        "bool want_ax, bool want_pre, bool y_bf16, int grid_reserve, float avg_nnz_per_row=-1.0) -> (Tensor, Tensor, Tensor)");
+  m.def("spmm_gemm_bf16_supported(int K, int Nf) -> bool", &spmm_gemm_bf16_supported);
   m.def("bgemm(Tensor A, Tensor W, bool trans_w, int act, bool want_pre, int algo) -> (Tensor, Tensor)");
   m.def("bgemm_dW(Tensor A, Tensor dY, bool per_slice, int algo) -> Tensor");
   m.def("bgemm_dW_act(Tensor A, Tensor dY, Tensor pre, int act, bool per_slice) -> Tensor");
@@ -1480,6 +1586,9 @@ TORCH_LIBRARY(tmgcn, m) {
   m.def("spmm_feature_gemm(Tensor X, Tensor W, Tensor rowptr, Tensor col, Tensor val, Tensor? t_rowptr, "
         "Tensor? t_col, Tensor? t_val, int N, float avg_nnz_per_row, int act, int grid_reserve, Tensor? giant_rows=None, "
         "Tensor? giant_chunks=None, Tensor? t_giant_rows=None, Tensor? t_giant_chunks=None) -> Tensor");
+  m.def("spmm_feature_gemm_bf16(Tensor X, Tensor W, Tensor rowptr, Tensor col, Tensor val, Tensor? t_rowptr, "
+        "Tensor? t_col, Tensor? t_val, int N, float avg_nnz_per_row, int act, bool y_bf16, int grid_reserve) -> Tensor");
+  m.def("round_bf16(Tensor x) -> Tensor");
   m.def("edge_head(Tensor Z, Tensor U, Tensor src, Tensor dst, Tensor? eptr, Tensor? eidx) -> Tensor");
   m.def("activation(Tensor x, int act) -> Tensor");
   m.def("layer12(Tensor H, Tensor W1, Tensor W2, Tensor rowptr, Tensor col, Tensor val, Tensor? t_rowptr, Tensor? t_col, "
@@ -1524,6 +1633,8 @@ static void impl_differentiable(torch::Library& m) {
   m.impl("spmm", &spmm_ad);
   m.impl("feature_gemm", &feature_gemm_ad);
   m.impl("spmm_feature_gemm", &spmm_feature_gemm_ad);
+  m.impl("spmm_feature_gemm_bf16", &spmm_feature_gemm_bf16_ad);
+  m.impl("round_bf16", &round_bf16_ad);
   m.impl("edge_head", &edge_head_ad);
   m.impl("activation", &activation_ad);
   m.impl("layer12", &layer12_ad);
@@ -1543,6 +1654,7 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("spmm_csr_batched", &spmm_csr_batched);
   m.impl("spmm_gemm", &spmm_gemm);
   m.impl("spmm_gemm_out", &spmm_gemm_out);
+  m.impl("spmm_gemm_bf16", &spmm_gemm_bf16);
   m.impl("bgemm", &bgemm);
   m.impl("bgemm_dW", &bgemm_dW);
   m.impl("bgemm_dW_act", &bgemm_dW_act);

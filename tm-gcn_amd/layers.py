@@ -382,15 +382,29 @@ class EmbeddingGCN_reg(_Deliver, nn.Module):
 
 
 class EmbeddingGCN2(_Head, _Deliver, _Sharding, nn.Module):
-    """2-layer TM-GCN (ehf:236-357).  ``group``: slice-shard the model over a process group (_Sharding)."""
+    """2-layer TM-GCN (ehf:236-357).  ``group``: slice-shard the model over a process group (_Sharding).
+    ``act_dtype=torch.bfloat16``: store the operand that layer 2 gathers in bf16 (see __init__)."""
 
     def __init__(self, At: AdjLike, X: torch.Tensor, edges: torch.Tensor, M: torch.Tensor,
                  hidden_feat=[2, 2, 2], condensed_W=False, use_Minv=True, apply_M_twice=False,
-                 apply_M_three_times=False, nonlin2="relu", device=None, param_dtype=torch.float32, group=None):
+                 apply_M_three_times=False, nonlin2="relu", device=None, param_dtype=torch.float32, group=None,
+                 act_dtype=None):
         super().__init__()
         dev = torch.device(device) if device is not None else _default_device()
         if nonlin2 not in _NONLIN:
             raise RuntimeError(f"nonlin2 must be one of {_NONLIN}")
+        # act_dtype=torch.bfloat16: the dense operand of layer 2's fused SpMM+GEMM — the layer-1 output, or its M-transform —
+        # is rounded to bf16 once and gathered by the bf16 kernel (half the gathered bytes); parameters, logits and the
+        # head stay fp32.  None (default): everything as before.
+        if act_dtype not in (None, torch.bfloat16):
+            raise RuntimeError(f"act_dtype must be None or torch.bfloat16, got {act_dtype}")
+        if act_dtype is not None:
+            if group is not None:
+                raise RuntimeError("act_dtype is not available together with group= (the sharded layer exchanges fp32 activations)")
+            if not ops.spmm_gemm_bf16_supported(hidden_feat[0], hidden_feat[1]):
+                raise RuntimeError(f"act_dtype=torch.bfloat16 needs hidden_feat[0] a multiple of 8 in [16,128] and hidden_feat[1] <= 128, "
+                                   f"got hidden_feat={list(hidden_feat)}")
+        self.act_dtype = act_dtype
         self.use_Minv = use_Minv
         self.apply_M_twice = apply_M_twice
         self.apply_M_three_times = apply_M_three_times
@@ -429,7 +443,7 @@ class EmbeddingGCN2(_Head, _Deliver, _Sharding, nn.Module):
             AtXt, eidx = self.AtXt, self._edges
         ps = not self.condensed_W
         W1, W2, U = self._p(self.W1, ps, gemm=True), self._p(self.W2, ps), self._p(self.U)
-        if not self.use_Minv and not self.apply_M_twice and not ps and self._shard is None:
+        if not self.use_Minv and not self.apply_M_twice and not ps and self._shard is None and self.act_dtype is None:
             # the as-run default branch (ehf:330-335 + 348-349): both layers in one launch each way, the layer-1
             # activations never stored (ops.layer12; the unfused pair where the widths do not allow it)
             return ops.layer12(AtXt, self._p(self.W1), self.nonlin2, self.At, W2), eidx, U, None
@@ -440,14 +454,15 @@ class EmbeddingGCN2(_Head, _Deliver, _Sharding, nn.Module):
             Y = ops.feature_gemm(AtXt, W1, act=self.nonlin2)
         # second layer — always the training adjacency self.At (ehf:339, 343, 348); sharded, the
         # M / M⁻¹ products below are the only steps that exchange activations between ranks
+        store = ops.round_bf16 if self.act_dtype is not None else (lambda x: x)    # the gathered operand, stored in act_dtype
         if self.use_Minv:
-            Z = self._mt(ops.spmm_feature_gemm(self.At, self._mt(Y, self.Mop), W2), self.Minv)
+            Z = self._mt(ops.spmm_feature_gemm(self.At, store(self._mt(Y, self.Mop)), W2), self.Minv)
         elif self.apply_M_twice:
-            Z = ops.spmm_feature_gemm(self.At, self._mt(Y, self.Mop), W2)
+            Z = ops.spmm_feature_gemm(self.At, store(self._mt(Y, self.Mop)), W2)
             if self.apply_M_three_times:
                 Z = self._mt(Z, self.Mop)                                          # ehf:346
         else:
-            Z = ops.spmm_feature_gemm(self.At, Y, W2)                              # ehf:348-349
+            Z = ops.spmm_feature_gemm(self.At, store(Y), W2)                       # ehf:348-349
         return Z, eidx, U, None
 
 

@@ -333,6 +333,19 @@ class HipKernels:
             float(A.avg_nnz_per_row), *A.giant_plan()))
         return Y, (AX if AX.numel() else None), (pre if pre.numel() else None)
 
+    # P2+P3 fused, the gathered operand stored in bf16 -------------------------------------
+    def spmm_gemm_bf16_supported(self, K: int, Nf: int) -> bool:
+        return bool(_lib.load().tmgcn_spmm_gemm_bf16_supported(K, Nf))
+
+    def spmm_gemm_bf16(self, A: BatchedCSR, X: torch.Tensor, W: torch.Tensor, trans_w=False, act=None, want_ax=False,
+                       want_pre=False, out_dtype=None, tag="spmm_gemm_bf16", grid_reserve=0):
+        """act((Â ⋆ X) · Wop) in one launch with X stored in bf16 (csrc/spmm_gemm_bf16.hip): half the gathered bytes.
+        Y in fp32 (out_dtype None) or bf16; AX and pre in fp32.  Returns (Y, AX or None, pre or None)."""
+        Y, AX, pre = self._run(tag, X.device, lambda: self.ops.spmm_gemm_bf16(
+            A.rowptr, A.col, A.val, X, A.N, W, bool(trans_w), _lib.ACT_IDS[act], bool(want_ax), bool(want_pre),
+            _y_bf16(out_dtype), int(grid_reserve), float(A.avg_nnz_per_row)))
+        return Y, (AX if AX.numel() else None), (pre if pre.numel() else None)
+
     # P3 ---------------------------------------------------------------------------------
     def gemm(self, A: torch.Tensor, W: torch.Tensor, trans_w=False, act=None, want_pre=False, algo=None):
         """A [T,N,K] · W ([K,Nf] shared or [T,K,Nf] per slice; transposed if trans_w).  W may be stored
@@ -537,11 +550,45 @@ def feature_gemm(A: torch.Tensor, W: torch.Tensor, act=None) -> torch.Tensor:
     return _FeatureGemm.apply(A, W, act)
 
 
-def spmm_feature_gemm(A: BatchedCSR, X: torch.Tensor, W: torch.Tensor, act=None, fuse: Optional[bool] = None):
+def _y_bf16(out_dtype) -> bool:
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise RuntimeError(f"out_dtype must be None, torch.float32 or torch.bfloat16, got {out_dtype}")
+    return out_dtype == torch.bfloat16
+
+
+def spmm_gemm_bf16_supported(K: int, Nf: int) -> bool:
+    """Widths of the bf16-stored fused SpMM+GEMM: K a multiple of 8 in [16,128], Nf <= 128."""
+    return kernels.name == "hip" and kernels.spmm_gemm_bf16_supported(int(K), int(Nf))
+
+
+def round_bf16(X: torch.Tensor) -> torch.Tensor:
+    """fp32 -> bf16, rounded to nearest even once by one cast launch; the gradient comes back widened to fp32."""
+    return kernels.ops.round_bf16(X)
+
+
+def spmm_feature_gemm(A: BatchedCSR, X: torch.Tensor, W: torch.Tensor, act=None, fuse: Optional[bool] = None, out_dtype=None):
     """P2 then P3 (+P5): act((Â ⋆ X) · W).  One fused launch when the kernel supports the
     widths (K a multiple of 8 in [16,128] with Nf <= 128, or K in {1,2,3,4,6,8} with Nf <= 16), else the two
-    kernels back to back."""
+    kernels back to back.
+
+    An X stored in bf16 takes the bf16 gather (csrc/spmm_gemm_bf16.hip: half the gathered bytes, fp32 accumulation, fp32
+    W): K a multiple of 8 in [16,128] with Nf <= 128, anything else raises — nothing is widened silently.  Y comes out in
+    `out_dtype` (None = fp32, or torch.bfloat16: rounded once); the gradient of X comes back in bf16.  With an fp32 X,
+    `out_dtype` must be None or fp32.  (The bf16 route always runs through the registered C++ autograd; a KernelTimer
+    times its launches through `kernels.spmm_gemm_bf16`, the kernel-level launcher.)"""
     K, Nf = X.shape[-1], W.shape[-1]
+    y_bf16 = _y_bf16(out_dtype)
+    if X.dtype == torch.bfloat16:
+        if not spmm_gemm_bf16_supported(K, Nf):
+            raise RuntimeError(f"the bf16-stored fused SpMM+GEMM does not support K={K}, Nf={Nf} "
+                               "(K a multiple of 8 in [16,128], Nf <= 128)")
+        if fuse is not None and not fuse:
+            raise RuntimeError("a bf16-stored X has the fused launch only (fuse=False asks for the fp32 pair)")
+        need = X.requires_grad and torch.is_grad_enabled()
+        return kernels.ops.spmm_feature_gemm_bf16(X, W, A.rowptr, A.col, A.val, *_csr_t(A, need), A.N, A.avg_nnz_per_row,
+                                                  _lib.ACT_IDS[act], y_bf16, 0)
+    if y_bf16:
+        raise RuntimeError("out_dtype=torch.bfloat16 needs an X stored in bf16; an fp32 X gives an fp32 Y")
     can = hasattr(kernels, "spmm_gemm_supported") and kernels.spmm_gemm_supported(K, Nf)
     if fuse is None:
         fuse = can
