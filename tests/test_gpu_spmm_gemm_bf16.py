@@ -19,7 +19,7 @@ from tmgcn_amd.csr import BatchedCSR
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF16 = torch.bfloat16
-WIDTHS = [(16, 8), (24, 40), (64, 64), (128, 128), (128, 16)]
+WIDTHS = [(16, 8), (24, 40), (64, 64), (120, 40), (128, 128), (128, 16)]
 
 
 def ref_spmm(csr, X):

@@ -61,175 +61,23 @@ struct FusedArgs {
   GiantPlan giant;             // rows summed chunk by chunk in front of this launch (spmm_row.h), or rows == nullptr
 };
 
-// Development build only (-DTMGCN_FUSED_TRACE, tools/fused_trace.py): thread 0 of every block sums the 100 MHz wall-clock time
-// it spends in each phase of its tiles — separately for short tiles (entry-major walk) and the others — and leaves the
-// sums in a device array read back through tmgcn_debug_fused_trace.  Not part of the library.
+// Development build only (-DTMGCN_FUSED_TRACE, tools/fused_trace.py; the stamps: spmm_gemm_tile.h): the per-block phase times
+// of this kernel, read back through tmgcn_debug_fused_trace.  Not part of the library.
 #ifdef TMGCN_FUSED_TRACE
 __device__ unsigned long long fused_trace_words[4096 * 16];
-#define FT_NOW() wall_clock64()
-#define FT_WAIT() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
-#define FT_STAMP(name) const unsigned long long name = FT_NOW()
+#define FT_WORDS fused_trace_words
 #else
-#define FT_STAMP(name) do { } while (0)
-#define FT_WAIT() do { } while (0)
+#define FT_WORDS nullptr
 #endif
 
-// ---- the gather of the fused kernel (its W fragments and product phase: spmm_gemm_tile.h) ----------------------------------------------------------------------------
-
-// Phase 1: the row sums of one tile into the LDS tile `As` ([64][FLDA]) and, when asked for, to AX; all four waves.
-// A tile of few entries entry-major, several rows per wave at once (spmm_row.h "Short tiles"); otherwise 16 rows per wave,
-// long rows afterwards on all four waves.
-template <int LPR, int U, int US>
-__device__ __forceinline__ void fused_gather_tile(const FusedArgs& a, float* As, float4* s_part, const TileRows& rows, int64_t row0,
-                                                  int64_t row_end, int lane, int wave, unsigned int* s_row) {
-  const int F4 = a.K / 4;
-  const int n_tile_rows = row_end - row0 < FBM ? (int)(row_end - row0) : FBM;
-  const int64_t slice0 = row0 / a.N;
-  const bool is_short = short_tile(rows, row0 + n_tile_rows <= (slice0 + 1) * a.N);
-  if (is_short) {
-    gather_short_tile<LPR, US>(a.col, a.val, a.X + slice0 * (int64_t)a.N * F4, rows, n_tile_rows, F4, lane, wave, F4,
-                               [&](int rr, const float4& acc, int fl) {
-                                 if (fl < F4) {
-                                   *reinterpret_cast<float4*>(&As[rr * FLDA + 4 * fl]) = acc;
-                                   if (a.AX) store_f4(&reinterpret_cast<float4*>(a.AX)[(row0 + rr) * F4 + fl], acc);
-                                 }
-                               });
-    return;
-  }
-  // The rows of the tile are DRAWN by the four waves (an LDS counter, 4 at the start of a tile; the draw is issued in front of
-  // the row it follows, so its latency hides under that row's gather): with a fixed deal — rows w, w + 4, … — the waves of a
-  // skewed tile met 10.9 us apart at the barrier behind this loop (power-law graph, traced; equal rows: 1.5).  A row is summed
-  // by whichever wave draws it, in the same order: the same bits.  Worth 0.3-0.5 % on the power-law graph (the launch is
-  // bandwidth-bound: the CU's other blocks fill the wait), nothing on equal rows (profiles/r6/r6_35_*).
-  for (int rr = wave; rr < FBM;) {
-    unsigned int nxt = 0;
-    if (lane == 0) nxt = atomicAdd(s_row, 1u);
-    const int64_t r = row0 + rr;
-    const bool lng = (rows.long_mask >> rr) & 1;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < row_end && !lng) {
-      const int64_t slice = r / a.N;
-      acc = gather_row<LPR, U>(a.col, a.val, a.X + slice * (int64_t)a.N * F4, readlane64(rows.beg, rr),
-                               readlane64(rows.end, rr), F4, lane);
-    }
-    if (!lng && lane < LPR && lane < F4) {
-      *reinterpret_cast<float4*>(&As[rr * FLDA + 4 * lane]) = acc;
-      if (a.AX && r < row_end) store_f4(&reinterpret_cast<float4*>(a.AX)[r * F4 + lane], acc);
-    }
-    rr = (int)__builtin_amdgcn_readfirstlane(nxt);
-  }
-  for (uint64_t m = rows.long_mask; m; m &= m - 1) {
-    const int rr = __builtin_ctzll(m);
-    const int64_t r = row0 + rr;
-    const int64_t slice = r / a.N;
-    const int64_t beg = readlane64(rows.beg, rr), end = readlane64(rows.end, rr);
-    float4 acc;
-    const int gi = (a.giant.rows && end - beg > kGiantRow) ? giant_find(a.giant, r) : -1;   // uniform over the four waves
-    if (gi >= 0) {
-      if (wave != (rr & 3)) continue;
-      acc = giant_row_sum(a.giant, gi, F4, lane, 0, F4);
-    } else {
-      acc = gather_long_row<LPR, U>(a.col, a.val, a.X + slice * (int64_t)a.N * F4, beg, end, F4, lane, wave, s_part);
-    }
-    if (wave == (rr & 3) && lane < LPR && lane < F4) {
-      *reinterpret_cast<float4*>(&As[rr * FLDA + 4 * lane]) = acc;
-      if (a.AX) store_f4(&reinterpret_cast<float4*>(a.AX)[r * F4 + lane], acc);
-    }
-  }
-}
-
+// The tile kernel: phase 1 (fused_gather_tile), the product phase and the persistent loop around them are spmm_gemm_tile.h's,
+// shared with the bf16-stored operand's kernel; this one gathers float4 pieces, with short tiles and the giant-row plan.
 template <int LPR, int U, int NJ, int US = TMGCN_FUSED_US * U>  // NJ = K / 8 (K is a multiple of 8 here)
 __global__ __launch_bounds__(256, TMGCN_FUSED_OCC) void spmm_gemm_kernel(FusedArgs a) {
   __shared__ float As[FBM * FLDA];
   __shared__ float4 s_part[4 * LPR];      // partial sums of a long row, one per wave (spmm_row.h)
-  const int lane0 = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n0 = wave * 32;
-  const TileMap tm = a.tiles;
-
-  float wreg[NJ][4];
-  int64_t cur_batch = -1;
   __shared__ unsigned int s_tile, s_row;
-  if (threadIdx.x == 0) s_row = 4;        // (the first use is behind the barrier of the first tile draw)
-  HeavyScan heavy;
-  heavy.init(a.rowptr, tm);
-
-#ifdef TMGCN_FUSED_TRACE
-  unsigned long long ft[16] = {0};        // [8·short + phase]: 0 draw, 1 row pointers, 2 gather (wave 0), 3 barrier, 4 products, 5 barrier, 6 tiles
-#endif
-  for (;;) {
-    // The lane index is laundered through an empty asm once per tile and once more in front of the product phase: what the
-    // two phases derive from it (feature lane, stream, LDS and output addresses) is then recomputed where it is used — a few
-    // VALU instructions — instead of being hoisted out of this loop and held in registers across the OTHER phase, where the
-    // 64 W fragments and the gather's loads in flight need them (round 6: two W fragments lived in scratch and were
-    // re-read inside the MFMA chain, four exposed loads per tile).
-    int lane = lane0;
-    asm volatile("" : "+v"(lane));
-    FT_STAMP(ft_a);
-    // next tile: first the heavy tiles (spmm_row.h: windows drawn from counter[1]), then from the device counter
-    // (counter[0]; ascending, so resident blocks stay inside one slice)
-    int64_t tile = -1;
-    if (heavy.scanning) tile = heavy.next(a.rowptr, tm, a.tile_counter + 1, &s_tile, lane);
-    const bool scanning = heavy.scanning;
-    if (!scanning) {
-      if (threadIdx.x == 0) s_tile = atomicAdd(a.tile_counter, 1u);
-      __syncthreads();
-      tile = s_tile;
-      if (tile >= a.n_tiles) break;
-    }
-    int64_t unit, row0, row_end;
-    tile_extent(tm, tile, unit, row0, row_end);
-    const int64_t batch = a.rows_per_batch ? row0 / a.rows_per_batch : 0;
-    FT_STAMP(ft_b);
-    TileRows rows;
-    rows.load(a.rowptr, row0, row_end, lane);
-    if (!scanning && rows.entries > heavy.thr) {   // done in somebody's pass 1
-      __syncthreads();                             // (s_tile is rewritten at the top)
-      continue;
-    }
-    FT_WAIT();
-    FT_STAMP(ft_c);
-    if (batch != cur_batch) {
-      fused_load_w<NJ>(a, batch, n0, lane & 31, lane >> 5, wreg);
-      cur_batch = batch;
-    }
-    fused_gather_tile<LPR, U, US>(a, As, s_part, rows, row0, row_end, lane, wave, &s_row);
-    FT_WAIT();
-    FT_STAMP(ft_d);
-    __syncthreads();
-    if (threadIdx.x == 0) s_row = 4;        // for the next tile's row draws (two barriers away)
-    FT_STAMP(ft_e);
-    // the product phase at raised issue priority: its waves hold the block's LDS tile and share the SIMD with three other
-    // blocks' waves that are waiting for gathered rows anyway (round 6: -4.5 % on the chess operand at bench size, -6 % at
-    // 4 random entries per row, S4 unchanged; profiles/r6/r6_08_*)
-    __builtin_amdgcn_s_setprio(TMGCN_FUSED_MFMA_PRIO);
-    {
-      int lane_p = lane0;
-      asm volatile("" : "+v"(lane_p));
-      fused_mfma_tile<NJ>(a, As, wreg, row0, row_end, n0, lane_p & 31, lane_p >> 5);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    FT_STAMP(ft_f);
-    __syncthreads();  // tile consumed before the next phase 1 overwrites it
-#ifdef TMGCN_FUSED_TRACE
-    {
-      const int n_tile_rows = row_end - row0 < FBM ? (int)(row_end - row0) : FBM;
-      const int k = short_tile(rows, row0 + n_tile_rows <= (row0 / a.N + 1) * a.N) ? 8 : 0;
-      const unsigned long long ft_g = FT_NOW();
-      ft[k + 0] += ft_b - ft_a;
-      ft[k + 1] += ft_c - ft_b;
-      ft[k + 2] += ft_d - ft_c;
-      ft[k + 3] += ft_e - ft_d;
-      ft[k + 4] += ft_f - ft_e;
-      ft[k + 5] += ft_g - ft_f;
-      ft[k + 6] += 1;
-    }
-#endif
-  }
-#ifdef TMGCN_FUSED_TRACE
-  if (threadIdx.x == 0 && blockIdx.x < 4096)
-    for (int i = 0; i < 16; ++i) fused_trace_words[blockIdx.x * 16 + i] = ft[i];
-#endif
+  fused_tile_loop<FusedF32, LPR, U, NJ, US, false>(a, As, s_part, &s_tile, &s_row, FT_WORDS);
 }
 
 
@@ -568,13 +416,10 @@ extern "C" int tmgcn_spmm_gemm_f32_plan(const int64_t* rowptr, const int32_t* co
                                          float avg_nnz_per_row, const int64_t* giant_rows, const int32_t* giant_chunks,
                                          int32_t n_giant, int32_t n_giant_chunks, float* giant_ws, int64_t giant_ws_bytes,
                                          void* stream) {
-  TMGCN_REQUIRE(grid_reserve >= 0 && grid_reserve <= 4096, "spmm_gemm: grid_reserve %d out of range [0, 4096]", grid_reserve);
-  TMGCN_REQUIRE(n_rows >= 0 && N > 0, "spmm_gemm: bad shape n_rows=%lld N=%d", (long long)n_rows, N);
-  TMGCN_REQUIRE(tmgcn_spmm_gemm_supported(K, Nf),
-                "spmm_gemm: unsupported widths K=%d Nf=%d (need K a multiple of 8 in [16,128] with Nf <= 128, or K in {1,2,3,4,6,8} with Nf <= 16); "
-                "use tmgcn_spmm_csr_batched_f32 + tmgcn_gemm_f32", K, Nf);
-  TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "spmm_gemm: unknown activation %d", act);
-  TMGCN_REQUIRE(rows_per_batch >= 0, "spmm_gemm: negative rows_per_batch");
+  const int bad = fused_check_args("spmm_gemm", grid_reserve, n_rows, N, K, Nf, tmgcn_spmm_gemm_supported(K, Nf),
+                                   "(need K a multiple of 8 in [16,128] with Nf <= 128, or K in {1,2,3,4,6,8} with Nf <= 16); "
+                                   "use tmgcn_spmm_csr_batched_f32 + tmgcn_gemm_f32", act, 0, rows_per_batch);
+  if (bad) return bad;
   if (n_rows == 0) return TMGCN_OK;
   TMGCN_REQUIRE(rowptr && X && W && Y, "spmm_gemm: null pointer");
   TMGCN_REQUIRE(n_rows % N == 0, "spmm_gemm: n_rows=%lld is not a multiple of N=%d", (long long)n_rows, N);
@@ -609,13 +454,9 @@ extern "C" int tmgcn_spmm_gemm_f32_plan(const int64_t* rowptr, const int32_t* co
     if (rc != TMGCN_OK) return rc;
     a.giant = GiantPlan{giant_rows, giant_chunks, reinterpret_cast<const float4*>(giant_ws), n_giant};
   }
-  // a unit of tiles = a slice, unless the caller's weight batches do not end on slice boundaries (no layer does that)
-  a.tiles = make_tile_map(n_rows, (rows_per_batch == 0 || rows_per_batch % N == 0) ? (int64_t)N : rows_per_batch);
-  a.n_tiles = a.tiles.n_tiles;
-  TMGCN_REQUIRE(a.n_tiles < (int64_t)0x7fffffff, "spmm_gemm: too many row tiles");
-  a.tile_counter = acquire_tile_counters((hipStream_t)stream, 2);      // [0] the main loop's tiles, [1] the heavy-tile scan windows
-  TMGCN_REQUIRE(a.tile_counter, "spmm_gemm: no tile counter: %s", pool_error());
   hipStream_t st = (hipStream_t)stream;
+  const int no_tiles = fused_plan_tiles("spmm_gemm", a, st);
+  if (no_tiles) return no_tiles;
   // few entries per row (the caller's hint), no giant-row plan, K = 64 or 128: the products on the bf16 matrix cores
   if (avg_nnz_per_row >= 0.f && avg_nnz_per_row < (float)TMGCN_BX3_MAX_DEG && n_giant == 0 && (K == 128 || K == 64)) {
     if (K == 128) {

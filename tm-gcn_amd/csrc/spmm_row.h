@@ -1,4 +1,5 @@
-// Row gather shared by the plain and the GEMM-fused SpMM kernels (gfx950).
+// Row gather shared by the plain and the GEMM-fused SpMM kernels (gfx950), written once over the 16-byte piece a lane loads:
+// float4 of fp32 (PieceF32, the default) or 8 bf16 values (PieceBf16).
 #pragma once
 #include "common.h"
 
@@ -15,23 +16,74 @@ __device__ __forceinline__ void store_f4(float4* p, const float4& v) {
 }
 __device__ __forceinline__ void store_f1(float* p, float v) { __builtin_nontemporal_store(v, p); }
 
+// The 16-byte PIECE of a feature row that one lane gathers, and the fp32 sums the lane keeps of it: the loaded type, the sums,
+// and zero / fma / add / the butterfly step on them.  The gathers below are written once over a piece type.
+struct PieceF32 {             // 4 fp32 values: float4 fl of the row, columns 4·fl .. 4·fl + 3
+  using Load = float4;
+  using Sum = float4;
+  static constexpr int kFloats = 4;
+  static __device__ __forceinline__ Load none() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+  static __device__ __forceinline__ Sum zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+  // (fma and the butterfly step of this piece are written out in gather_row: see there)
+  static __device__ __forceinline__ void add(Sum& s, const Sum& t) {
+    s.x += t.x;
+    s.y += t.y;
+    s.z += t.z;
+    s.w += t.w;
+  }
+  static __device__ __forceinline__ const float4& quad(const Sum& s, int) { return s; }
+};
+struct Sum8 {                 // the 8 fp32 sums of a lane: columns 8·fl .. 8·fl + 7 of the row
+  float4 lo, hi;
+};
+struct PieceBf16 {            // 8 bf16 values, widened to fp32 as they are used — exact: a bf16 is the upper half of an fp32
+  using Load = uint4;
+  using Sum = Sum8;
+  static constexpr int kFloats = 8;
+  static __device__ __forceinline__ Load none() { return make_uint4(0u, 0u, 0u, 0u); }
+  static __device__ __forceinline__ Sum zero() { return Sum8{make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)}; }
+  // acc += v · widen(x): dword d of the piece holds value 2d in its low half and 2d + 1 in its high half
+  static __device__ __forceinline__ void fma(Sum& s, float v, const Load& x) {
+    s.lo.x = fmaf(v, __uint_as_float(x.x << 16), s.lo.x);
+    s.lo.y = fmaf(v, __uint_as_float(x.x & 0xffff0000u), s.lo.y);
+    s.lo.z = fmaf(v, __uint_as_float(x.y << 16), s.lo.z);
+    s.lo.w = fmaf(v, __uint_as_float(x.y & 0xffff0000u), s.lo.w);
+    s.hi.x = fmaf(v, __uint_as_float(x.z << 16), s.hi.x);
+    s.hi.y = fmaf(v, __uint_as_float(x.z & 0xffff0000u), s.hi.y);
+    s.hi.z = fmaf(v, __uint_as_float(x.w << 16), s.hi.z);
+    s.hi.w = fmaf(v, __uint_as_float(x.w & 0xffff0000u), s.hi.w);
+  }
+  static __device__ __forceinline__ void add(Sum& s, const Sum& t) {
+    PieceF32::add(s.lo, t.lo);
+    PieceF32::add(s.hi, t.hi);
+  }
+  static __device__ __forceinline__ void xor_add(Sum& s, int o) {   // s += the sums of lane ^ o
+    Sum8 t;
+    t.lo.x = __shfl_xor(s.lo.x, o);  t.lo.y = __shfl_xor(s.lo.y, o);  t.lo.z = __shfl_xor(s.lo.z, o);  t.lo.w = __shfl_xor(s.lo.w, o);
+    t.hi.x = __shfl_xor(s.hi.x, o);  t.hi.y = __shfl_xor(s.hi.y, o);  t.hi.z = __shfl_xor(s.hi.z, o);  t.hi.w = __shfl_xor(s.hi.w, o);
+    add(s, t);
+  }
+  static __device__ __forceinline__ const float4& quad(const Sum& s, int j) { return j ? s.hi : s.lo; }
+};
+
 // One wave sums one CSR row:  acc = sum_p val[p] * Xs[col[p]]  over [beg, end).
-// LPR lanes cover the F4 float4s of a feature row (lane fl), S = 64/LPR streams split the
+// LPR lanes cover the F pieces of a feature row (lane fl), S = 64/LPR streams split the
 // non-zeros; the row's (col,val) pairs are fetched 64 at a time with one coalesced load per
 // array and handed to the streams with ds_bpermute (__shfl); U 16-B gathers in flight per lane.
 // On return every lane of stream 0 (sub == 0) holds the full sum (fixed butterfly order).
-// `stride4` = row pitch of Xs in float4 (default: F4, a dense [N][F] matrix); a wider matrix is gathered as column chunks.
-template <int LPR, int U>
-__device__ __forceinline__ float4 gather_row(const int32_t* __restrict__ col,
-                                             const float* __restrict__ val,
-                                             const float4* __restrict__ Xs, int64_t beg,
-                                             int64_t end, int F4, int lane, int stride4 = 0) {
-  if (stride4 == 0) stride4 = F4;
+// `stride` = row pitch of Xs in pieces (default: F, a dense [N][F] matrix); a wider matrix is gathered as column chunks.
+// OFF32: the slice of X is smaller than 4 GiB, so a piece's address is the slice's (scalar) base + a 32-bit byte offset —
+// one address register per gather in flight instead of two (what that buys: the launcher of spmm_gemm_bf16.hip).
+template <int LPR, int U, class P = PieceF32, bool OFF32 = false>
+__device__ __forceinline__ typename P::Sum gather_row(const int32_t* __restrict__ col, const float* __restrict__ val,
+                                                      const typename P::Load* __restrict__ Xs, int64_t beg, int64_t end, int F,
+                                                      int lane, int stride = 0) {
+  if (stride == 0) stride = F;
   constexpr int S = kWave / LPR;
   const int sub = lane / LPR;
   const int fl = lane % LPR;
-  const bool f_ok = fl < F4;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  const bool f_ok = fl < F;
+  typename P::Sum acc = P::zero();
   for (int64_t base = beg; base < end; base += kWave) {
     const int n = (int)((end - base) < kWave ? (end - base) : kWave);
     int c = 0;
@@ -41,32 +93,45 @@ __device__ __forceinline__ float4 gather_row(const int32_t* __restrict__ col,
       v = val[base + lane];
     }
     for (int p = 0; p < n; p += S * U) {
-      float4 x[U];
+      typename P::Load x[U];
       float vv[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int idx = p + u * S + sub;
         const int cc = __shfl(c, idx & 63);
         vv[u] = __shfl(v, idx & 63);
-        x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (idx < n && f_ok) x[u] = Xs[(int64_t)cc * stride4 + fl];
+        x[u] = P::none();
+        if (idx < n && f_ok) {
+          if (OFF32) x[u] = *reinterpret_cast<const typename P::Load*>(reinterpret_cast<const char*>(Xs) + (uint32_t)(cc * stride + fl) * 16u);
+          else x[u] = Xs[(int64_t)cc * stride + fl];
+        }
         if (idx >= n) vv[u] = 0.f;
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        acc.x = fmaf(vv[u], x[u].x, acc.x);
-        acc.y = fmaf(vv[u], x[u].y, acc.y);
-        acc.z = fmaf(vv[u], x[u].z, acc.z);
-        acc.w = fmaf(vv[u], x[u].w, acc.w);
+        // float4 pieces: written out here.  Through PieceF32 members hipcc allocates the fp32 kernels' registers differently
+        // (same VGPRs, two SGPRs fewer, thousands of lines of other code); this form compiles to the code it always was.
+        if constexpr (std::is_same<P, PieceF32>::value) {
+          acc.x = fmaf(vv[u], x[u].x, acc.x);
+          acc.y = fmaf(vv[u], x[u].y, acc.y);
+          acc.z = fmaf(vv[u], x[u].z, acc.z);
+          acc.w = fmaf(vv[u], x[u].w, acc.w);
+        } else {
+          P::fma(acc, vv[u], x[u]);
+        }
       }
     }
   }
 #pragma unroll
   for (int o = LPR; o < kWave; o <<= 1) {
-    acc.x += __shfl_xor(acc.x, o);
-    acc.y += __shfl_xor(acc.y, o);
-    acc.z += __shfl_xor(acc.z, o);
-    acc.w += __shfl_xor(acc.w, o);
+    if constexpr (std::is_same<P, PieceF32>::value) {
+      acc.x += __shfl_xor(acc.x, o);
+      acc.y += __shfl_xor(acc.y, o);
+      acc.z += __shfl_xor(acc.z, o);
+      acc.w += __shfl_xor(acc.w, o);
+    } else {
+      P::xor_add(acc, o);
+    }
   }
   return acc;
 }
@@ -173,30 +238,25 @@ struct TileRows {
   }
 };
 
-// A long row on four waves: wave w gathers quarter w, the partial sums meet in `part` ([4][LPR] float4 of LDS) and
-// lanes < LPR of EVERY wave return ((p0 + p1) + p2) + p3.  Called by all 256 threads; two block barriers.
-template <int LPR, int U>
-__device__ __forceinline__ float4 gather_long_row(const int32_t* __restrict__ col, const float* __restrict__ val,
-                                                  const float4* __restrict__ Xs, int64_t beg, int64_t end, int F4, int lane,
-                                                  int wave, float4* part, int stride4 = 0) {
+// A long row on four waves: wave w gathers quarter w — a multiple of 64 entries —, the partial sums meet in `part`
+// ([4][LPR] sums of LDS) and lanes < LPR of EVERY wave return ((p0 + p1) + p2) + p3.  Called by all 256 threads; two block
+// barriers.
+template <int LPR, int U, class P = PieceF32, bool OFF32 = false>
+__device__ __forceinline__ typename P::Sum gather_long_row(const int32_t* __restrict__ col, const float* __restrict__ val,
+                                                           const typename P::Load* __restrict__ Xs, int64_t beg, int64_t end,
+                                                           int F, int lane, int wave, typename P::Sum* part, int stride = 0) {
   const int64_t q = (((end - beg + 3) >> 2) + (kWave - 1)) & ~(int64_t)(kWave - 1);
   int64_t b = beg + wave * q, e = b + q;
   if (b > end) b = end;
   if (e > end) e = end;
-  const float4 p = gather_row<LPR, U>(col, val, Xs, b, e, F4, lane, stride4);
+  const typename P::Sum p = gather_row<LPR, U, P, OFF32>(col, val, Xs, b, e, F, lane, stride);
   if (lane < LPR) part[wave * LPR + lane] = p;
   __syncthreads();
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  typename P::Sum s = P::zero();
   if (lane < LPR) {
     s = part[lane];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float4 t = part[w * LPR + lane];
-      s.x += t.x;
-      s.y += t.y;
-      s.z += t.z;
-      s.w += t.w;
-    }
+    for (int w = 1; w < 4; ++w) P::add(s, part[w * LPR + lane]);
   }
   __syncthreads();
   return s;

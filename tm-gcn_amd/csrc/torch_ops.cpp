@@ -208,6 +208,15 @@ void spmm_gemm_launch(const Tensor& rowptr, const Tensor& col, const Tensor& val
      "tmgcn_spmm_gemm_f32");
 }
 
+// Y (dtype y_dt) and the fp32 AX / pre of a fused SpMM + GEMM over X [T,N,K] with output width wn; an output that is not
+// asked for is an empty tensor (ptr(): nullptr), which is also what the operators return for it.
+static std::tuple<Tensor, Tensor, Tensor> fused_outputs(const Tensor& X, int64_t N, int64_t wn, at::ScalarType y_dt, bool want_ax,
+                                                        bool want_pre) {
+  const auto f32 = X.options().dtype(at::kFloat);
+  return {at::empty({X.size(0), N, wn}, f32.dtype(y_dt)), want_ax ? at::empty(X.sizes(), f32) : at::empty({0}, f32),
+          want_pre ? at::empty({X.size(0), N, wn}, f32) : at::empty({0}, f32)};
+}
+
 std::tuple<Tensor, Tensor, Tensor> spmm_gemm(const Tensor& rowptr, const Tensor& col, const Tensor& val,
                                              const Tensor& X, int64_t N, const Tensor& W, bool trans_w,
                                              int64_t act, bool want_ax, bool want_pre, int64_t grid_reserve,
@@ -218,12 +227,10 @@ std::tuple<Tensor, Tensor, Tensor> spmm_gemm(const Tensor& rowptr, const Tensor&
   check_csr(rowptr, col, val, X, N, "spmm_gemm");
   c10::DeviceGuard g(X.device());
   const WShape s = w_shape(W, trans_w, X.size(0), X.size(2), "spmm_gemm");
-  Tensor Y = at::empty({X.size(0), N, s.wn}, X.options());
-  Tensor AX = want_ax ? at::empty(X.sizes(), X.options()) : Tensor();
-  Tensor pre = (want_pre && act != TMGCN_ACT_NONE) ? at::empty_like(Y) : Tensor();
+  auto [Y, AX, pre] = fused_outputs(X, N, s.wn, at::kFloat, want_ax, want_pre && act != TMGCN_ACT_NONE);
   spmm_gemm_launch(rowptr, col, val, aligned16(X), N, W, trans_w, act, Y, AX, pre, grid_reserve, avg_nnz_per_row, giant_rows,
                    giant_chunks);
-  return {Y, AX.defined() ? AX : none_like(X), pre.defined() ? pre : none_like(X)};
+  return {Y, AX, pre};
 }
 
 // writes into caller-provided (views of) tensors: the slice-by-slice pipelined multi-GPU path
@@ -635,17 +642,14 @@ std::tuple<Tensor, Tensor, Tensor> spmm_gemm_bf16(const Tensor& rowptr, const Te
   check_csr(rowptr, col, val, X, N, "spmm_gemm_bf16");
   c10::DeviceGuard g(X.device());
   const WShape s = w_shape(W, trans_w, X.size(0), X.size(2), "spmm_gemm_bf16");
-  const auto f32 = X.options().dtype(at::kFloat);
-  Tensor Y = at::empty({X.size(0), N, s.wn}, y_bf16 ? X.options() : f32);
-  Tensor AX = want_ax ? at::empty(X.sizes(), f32) : Tensor();
-  Tensor pre = (want_pre && act != TMGCN_ACT_NONE) ? at::empty({X.size(0), N, s.wn}, f32) : Tensor();
+  auto [Y, AX, pre] = fused_outputs(X, N, s.wn, y_bf16 ? at::kBFloat16 : at::kFloat, want_ax, want_pre && act != TMGCN_ACT_NONE);
   const Tensor Xa = aligned16(X);
   ok(tmgcn_spmm_gemm_bf16((const int64_t*)ptr(rowptr), (const int32_t*)ptr(col), (const float*)ptr(val),
                           (const uint16_t*)ptr(Xa), X.size(0) * N, (int32_t)N, (int32_t)X.size(2), (const float*)ptr(W),
                           (int32_t)s.wn, trans_w ? 1 : 0, s.per_slice ? N : 0, s.stride, (int32_t)act, ptr(Y), y_bf16 ? 1 : 0,
                           (float*)ptr(AX), (float*)ptr(pre), (int32_t)grid_reserve, (float)avg_nnz_per_row, stream_of(X)),
      "tmgcn_spmm_gemm_bf16");
-  return {Y, AX.defined() ? AX : none_like(W), pre.defined() ? pre : none_like(W)};
+  return {Y, AX, pre};
 }
 
 // fp32 -> bf16, rounded to nearest even once (one cast launch); backward: the gradient widened to fp32
@@ -1030,6 +1034,34 @@ struct FeatureGemmFn : public torch::autograd::Function<FeatureGemmFn> {
   }
 };
 
+// What the two fused SpMM + GEMM functions keep for their backward: W, AX, pre, the transposed CSR when X needs a gradient
+// (saved variables 0-5), whatever `more` the function adds behind them, and N, avg, act, reserve.
+static void fused_save(AutogradContext* ctx, const char* who, const Tensor& W, const Tensor& AX, const Tensor& pre,
+                       const OptTensor& t_rowptr, const OptTensor& t_col, const OptTensor& t_val, bool need_x, variable_list more,
+                       int64_t N, double avg, int64_t act, int64_t grid_reserve) {
+  if (need_x)
+    TORCH_CHECK(t_rowptr.has_value() && t_col.has_value() && t_val.has_value(), who,
+                ": X requires grad but no transposed adjacency was passed");
+  more.insert(more.begin(), {W, AX, pre, need_x ? *t_rowptr : Tensor(), need_x ? *t_col : Tensor(), need_x ? *t_val : Tensor()});
+  ctx->save_for_backward(more);
+  ctx->saved_data["N"] = N;
+  ctx->saved_data["avg"] = avg;
+  ctx->saved_data["act"] = act;
+  ctx->saved_data["reserve"] = grid_reserve;
+}
+
+// dX = Âᵀ(dY·Wᵀ) in fp32 from what fused_save kept: (Âᵀ·dY)·Wᵀ, the fused kernel on dY, where the transposed widths have
+// one; else dA = dY·Wᵀ, then Âᵀ·dA.  gr, gc: the giant-row plan of the transposed CSR, if any.
+static Tensor fused_dx_f32(AutogradContext* ctx, const variable_list& sv, const Tensor& dY, const OptTensor& gr, const OptTensor& gc) {
+  const Tensor& W = sv[0];
+  const int64_t N = ctx->saved_data["N"].toInt();
+  const double avg = ctx->saved_data["avg"].toDouble();
+  if (spmm_gemm_supported(dY.size(-1), W.size(-2)))
+    return std::get<0>(spmm_gemm(sv[3], sv[4], sv[5], dY, N, W, true, TMGCN_ACT_NONE, false, false,
+                                 ctx->saved_data["reserve"].toInt(), avg, gr, gc));
+  return spmm_csr_batched(sv[3], sv[4], sv[5], std::get<0>(bgemm(dY, W, true, TMGCN_ACT_NONE, false, TMGCN_GEMM_AUTO)), N, avg, gr, gc);
+}
+
 struct SpmmFeatureGemmFn : public torch::autograd::Function<SpmmFeatureGemmFn> {
   // Fused P2+P3.  Backward uses Âᵀ(dY·Wᵀ) = (Âᵀ·dY)·Wᵀ: the same fused kernel on dY.
   static Tensor forward(AutogradContext* ctx, const Tensor& X, const Tensor& W, const Tensor& rowptr,
@@ -1039,35 +1071,22 @@ struct SpmmFeatureGemmFn : public torch::autograd::Function<SpmmFeatureGemmFn> {
                         const OptTensor& t_g_chunks, bool need_x, bool need_w) {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto [Y, AX, pre] = spmm_gemm(rowptr, col, val, X, N, W, false, act, need_w, need_x || need_w, grid_reserve, avg, g_rows, g_chunks);
-    if (need_x)
-      TORCH_CHECK(t_rowptr.has_value() && t_col.has_value() && t_val.has_value(),
-                  "spmm_feature_gemm: X requires grad but no transposed adjacency was passed");
     const bool tg = need_x && t_g_rows.has_value() && t_g_chunks.has_value();
-    ctx->save_for_backward({W, AX, pre, need_x ? *t_rowptr : Tensor(), need_x ? *t_col : Tensor(),
-                            need_x ? *t_val : Tensor(), tg ? *t_g_rows : none_like(X), tg ? *t_g_chunks : none_like(X)});
-    ctx->saved_data["N"] = N;
-    ctx->saved_data["avg"] = avg;
-    ctx->saved_data["act"] = act;
-    ctx->saved_data["reserve"] = grid_reserve;
+    fused_save(ctx, "spmm_feature_gemm", W, AX, pre, t_rowptr, t_col, t_val, need_x,
+               {tg ? *t_g_rows : none_like(X), tg ? *t_g_chunks : none_like(X)}, N, avg, act, grid_reserve);
     return Y;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto sv = ctx->get_saved_variables();
     const Tensor &W = sv[0], &AX = sv[1], &pre = sv[2];
-    const int64_t N = ctx->saved_data["N"].toInt(), act = ctx->saved_data["act"].toInt();
+    const int64_t act = ctx->saved_data["act"].toInt();
     Tensor dY = grads[0].contiguous();
     if (act != TMGCN_ACT_NONE) dY = act_bwd(pre, dY, act);
     Tensor dX, dW;
     if (ctx->needs_input_grad(0)) {
       const bool tg = sv[6].numel() > 0;
-      const OptTensor gr = tg ? OptTensor(sv[6]) : OptTensor(), gc = tg ? OptTensor(sv[7]) : OptTensor();
-      if (spmm_gemm_supported(dY.size(-1), W.size(-2)))
-        dX = std::get<0>(spmm_gemm(sv[3], sv[4], sv[5], dY, N, W, true, TMGCN_ACT_NONE, false, false,
-                                   ctx->saved_data["reserve"].toInt(), ctx->saved_data["avg"].toDouble(), gr, gc));
-      else  // the transposed widths have no fused kernel: dA = dY·Wᵀ, then Âᵀ·dA
-        dX = spmm_csr_batched(sv[3], sv[4], sv[5], std::get<0>(bgemm(dY, W, true, TMGCN_ACT_NONE, false, TMGCN_GEMM_AUTO)), N,
-                              ctx->saved_data["avg"].toDouble(), gr, gc);
+      dX = fused_dx_f32(ctx, sv, dY, tg ? OptTensor(sv[6]) : OptTensor(), tg ? OptTensor(sv[7]) : OptTensor());
     }
     if (ctx->needs_input_grad(1)) dW = bgemm_dW(AX, dY, W.dim() == 3, TMGCN_DW_AUTO);
     variable_list out(18);
@@ -1085,14 +1104,7 @@ struct SpmmFeatureGemmBf16Fn : public torch::autograd::Function<SpmmFeatureGemmB
                         double avg, int64_t act, bool y_bf16, int64_t grid_reserve, bool need_x, bool need_w) {
     at::AutoDispatchBelowADInplaceOrView guard;
     auto [Y, AX, pre] = spmm_gemm_bf16(rowptr, col, val, X, N, W, false, act, need_w, need_x || need_w, y_bf16, grid_reserve, avg);
-    if (need_x)
-      TORCH_CHECK(t_rowptr.has_value() && t_col.has_value() && t_val.has_value(),
-                  "spmm_feature_gemm_bf16: X requires grad but no transposed adjacency was passed");
-    ctx->save_for_backward({W, AX, pre, need_x ? *t_rowptr : Tensor(), need_x ? *t_col : Tensor(), need_x ? *t_val : Tensor()});
-    ctx->saved_data["N"] = N;
-    ctx->saved_data["avg"] = avg;
-    ctx->saved_data["act"] = act;
-    ctx->saved_data["reserve"] = grid_reserve;
+    fused_save(ctx, "spmm_feature_gemm_bf16", W, AX, pre, t_rowptr, t_col, t_val, need_x, {}, N, avg, act, grid_reserve);
     return Y;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
@@ -1113,15 +1125,8 @@ struct SpmmFeatureGemmBf16Fn : public torch::autograd::Function<SpmmFeatureGemmB
         if (!dYb.defined()) dYb = cast_multi({dY}, true)[0];
         dX = std::get<0>(spmm_gemm_bf16(sv[3], sv[4], sv[5], dYb, N, W, true, TMGCN_ACT_NONE, false, false, true,
                                         ctx->saved_data["reserve"].toInt(), avg));
-      } else {  // the transposed widths are outside the bf16 kernel's domain: the fp32 pair on the widened dY, rounded once
-        Tensor d32;
-        if (spmm_gemm_supported(dY.size(-1), W.size(-2)))
-          d32 = std::get<0>(spmm_gemm(sv[3], sv[4], sv[5], dY, N, W, true, TMGCN_ACT_NONE, false, false,
-                                      ctx->saved_data["reserve"].toInt(), avg, OptTensor(), OptTensor()));
-        else
-          d32 = spmm_csr_batched(sv[3], sv[4], sv[5], std::get<0>(bgemm(dY, W, true, TMGCN_ACT_NONE, false, TMGCN_GEMM_AUTO)), N, avg,
-                                 OptTensor(), OptTensor());
-        dX = cast_multi({d32}, true)[0];
+      } else {  // the transposed widths are outside the bf16 kernel's domain: the fp32 path on the widened dY, rounded once
+        dX = cast_multi({fused_dx_f32(ctx, sv, dY, OptTensor(), OptTensor())}, true)[0];
       }
     }
     if (ctx->needs_input_grad(1)) dW = bgemm_dW(AX, dY, W.dim() == 3, TMGCN_DW_AUTO);
