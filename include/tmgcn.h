@@ -46,7 +46,8 @@ enum { TMGCN_ACT_NONE = 0, TMGCN_ACT_RELU = 1, TMGCN_ACT_LEAKY = 2, TMGCN_ACT_SE
 
 /* Additions to ABI version 5 (backward compatible, the version stays 5): the WD-GCN entry points tmgcn_wdgcn_*, their
  * wide counterparts tmgcn_wdgcn_wide_* (widths up to 64) and the EvolveGCN-H entry points tmgcn_egcn_* and
- * tmgcn_egcn_wide_* (below).
+ * tmgcn_egcn_wide_* (below); tmgcn_mtransform_bf16 / tmgcn_mtransform_bf16_supported (the band M-transform on operands
+ * stored in bf16).
  * ABI version 5 = version 4 + tmgcn_pool_stats + the row_blocks partition argument of tmgcn_layer12_fwd/bwd_f32, the backward's AX / dW2 pair and tmgcn_layer12_bwd_forms_dw2 + tmgcn_head_loss_combine_f32 / tmgcn_head_loss_lanes (split rows of the one-pass head + loss plan) + the giant-row
  *   plan entry points tmgcn_spmm_csr_batched_f32_plan / tmgcn_spmm_gemm_f32_plan / tmgcn_spmm_giant_workspace_bytes; the launchers' scratch words (tile counters, hand-off blocks) are kept apart
  *   per stream (eager launches) and per recorded launch (hipGraph capture), and a launcher that cannot keep two launches
@@ -115,6 +116,27 @@ int tmgcn_mtransform_ld_f32(const float* M, int32_t Tm, int32_t ldm, int32_t tra
                             int32_t band_lo, int32_t band_hi,
                             const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t C,
                             int32_t x_group_rows, int32_t y_group_rows, void* stream);
+
+/* The band M-transform with X and / or Y STORED in bf16 (additions to ABI 5) — the M product in front of the layer-2 gather
+ * of a model that keeps its activations in bf16 (ehf:204, 308, 346), and autograd's Mᵀ product on that gather's bf16
+ * gradient.  The same product as tmgcn_mtransform_f32, plain row order, no column window:
+ *   X is [T_in][C] fp32 (x_bf16 = 0) or bf16 bit patterns (x_bf16 = 1), Y is [T_out][C] fp32 (y_bf16 = 0) or bf16 (1).
+ * Numerics: a bf16 X is widened on load (exact); every output element is the fp32 value the band kernel of
+ * tmgcn_mtransform_f32 computes (the same taps in the same order through fmaf); a bf16 Y is that value rounded to nearest
+ * even once.  For finite inputs the result is therefore bit for bit the composition  cast(tmgcn_mtransform_f32(cast(X)))
+ * — one launch and 6 B per element (fp32 -> bf16, bf16 -> fp32) instead of two launches and 14 B.  No atomics:
+ * bit-reproducible.  One read of X and one write of Y; C a multiple of 4 with X and Y aligned to four of their elements
+ * (16 B fp32, 8 B bf16) takes the four-columns-per-lane form, anything else one column per lane.
+ * Supported when tmgcn_mtransform_bf16_supported(band_lo, band_hi) != 0: band_lo, band_hi >= 0 and
+ * band_lo + band_hi + 1 <= 20 (every M of the reference; Minv and dense operators keep tmgcn_mtransform_f32 and the casts).
+ * TMGCN_ERR_INVALID, and no launch, on: the shape errors of tmgcn_mtransform_f32, a flag outside {0, 1}, both flags 0
+ * (that is tmgcn_mtransform_f32), an unsupported band, a NULL pointer, X == Y, a bf16 operand that is not 2-byte or an
+ * fp32 operand that is not 4-byte aligned.  TMGCN_OK without a launch when T_out == 0 or C == 0. */
+int tmgcn_mtransform_bf16_supported(int32_t band_lo, int32_t band_hi);
+int tmgcn_mtransform_bf16(const float* M, int32_t Tm, int32_t ldm, int32_t transpose,
+                          int32_t row_off, int32_t col_off, int32_t T_out, int32_t T_in,
+                          int32_t band_lo, int32_t band_hi,
+                          const void* X, int32_t x_bf16, void* Y, int32_t y_bf16, int64_t C, void* stream);
 
 /* ---- P2: batched CSR SpMM (per-frontal-slice Â_k · X_k) -------------------------
  * Replaces the loops  for k in range(T): AtXt[k] = t.sparse.mm(At[k], Xt[k])

@@ -33,6 +33,8 @@ SIGNATURES = {
     "tmgcn_pool_stats": (C.c_int, [_p, _i32]),
     "tmgcn_mtransform_f32": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, _i32, _i32, _p]),
     "tmgcn_mtransform_ld_f32": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64, _p, _i64, _i64, _i32, _i32, _p]),
+    "tmgcn_mtransform_bf16_supported": (C.c_int, [_i32, _i32]),
+    "tmgcn_mtransform_bf16": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _i32, _i64, _p]),
     "tmgcn_spmm_csr_batched_f32": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     "tmgcn_spmm_csr_batched_f32_hint": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _i32, C.c_float, _p]),
     "tmgcn_spmm_giant_workspace_bytes": (_i64, [_i32, _i32]),

@@ -6,6 +6,7 @@
 //
 //   kernel-level ops (one C-ABI launch each, no autograd)
 //     tmgcn::mtransform          tmgcn_mtransform_f32              ehf:204, 308, 346, 404; Minv ehf:224
+//     tmgcn::mtransform_bf16     tmgcn_mtransform_bf16             the band operators of the same, X and / or Y stored in bf16
 //     tmgcn::spmm_csr_batched    tmgcn_spmm_csr_batched_f32_hint   ehf:206-207, 303-304, 310-311, 471-472
 //     tmgcn::spmm_gemm(_out)     tmgcn_spmm_gemm_f32               the two statements above + ehf:222 in one launch
 //     tmgcn::spmm_gemm_bf16      tmgcn_spmm_gemm_bf16              the same launch on an X stored in bf16
@@ -19,7 +20,7 @@
 //     tmgcn::egcn_fwd/bwd        tmgcn_egcn_fwd / _bwd             evolvegcn_functions.py:80-95 (EvolveGCN-H)
 //     tmgcn::egcn_wide_fwd/bwd   tmgcn_egcn_wide_fwd / _bwd        the same at widths up to 64
 //   differentiable ops (registered under the Autograd key)
-//     tmgcn::m_transform, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm(_bf16), tmgcn::round_bf16,
+//     tmgcn::m_transform, tmgcn::m_transform_bf16, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm(_bf16), tmgcn::round_bf16,
 //     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce, tmgcn::wdgcn_lstm, tmgcn::egcn_evolve, tmgcn::egcn_evolve_wide
 //
 // No kernels live here: every launch goes through the C-ABI shared library (libtmgcn_hip.so),
@@ -120,6 +121,32 @@ void mtransform_out(const Tensor& M, const Tensor& X, Tensor Y, bool transpose, 
                              (int32_t)band_hi, (const float*)ptr(X), ldx, (float*)ptr(Y), ldy, C, (int32_t)x_group_rows,
                              (int32_t)y_group_rows, stream_of(X)),
      "tmgcn_mtransform_ld_f32");
+}
+
+// The band M-transform with X and / or Y stored in bf16 (csrc/mtransform_bf16.hip): X fp32 or bf16, Y allocated in bf16
+// (out_bf16) or fp32; one launch, the cast folded into the load / the store.  An fp32 X with an fp32 Y is tmgcn::mtransform.
+bool mtransform_bf16_supported(int64_t band_lo, int64_t band_hi) {
+  return band_lo <= INT32_MAX && band_hi <= INT32_MAX && tmgcn_mtransform_bf16_supported((int32_t)band_lo, (int32_t)band_hi) != 0;
+}
+Tensor mtransform_bf16(const Tensor& M, const Tensor& X, bool transpose, int64_t row_off, int64_t col_off, int64_t T_out,
+                       int64_t band_lo, int64_t band_hi, bool out_bf16) {
+  want(M, "mtransform_bf16 M");
+  const bool x_bf16 = X.defined() && X.scalar_type() == at::kBFloat16;
+  want(X, "mtransform_bf16 X", x_bf16 ? at::kBFloat16 : at::kFloat);
+  TORCH_CHECK(M.dim() == 2 && M.size(0) == M.size(1), "mtransform_bf16: M must be square");
+  TORCH_CHECK(X.dim() >= 1, "mtransform_bf16: X needs a leading time mode");
+  c10::DeviceGuard g(X.device());
+  const int64_t T_in = X.size(0);
+  if (T_out < 0) T_out = T_in;
+  const int64_t C = T_in ? X.numel() / T_in : 0;
+  auto sizes = X.sizes().vec();
+  sizes[0] = T_out;
+  Tensor Y = at::empty(sizes, X.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+  ok(tmgcn_mtransform_bf16((const float*)ptr(M), (int32_t)M.size(0), (int32_t)M.size(0), transpose ? 1 : 0, (int32_t)row_off,
+                           (int32_t)col_off, (int32_t)T_out, (int32_t)T_in, (int32_t)band_lo, (int32_t)band_hi, ptr(X),
+                           x_bf16 ? 1 : 0, ptr(Y), out_bf16 ? 1 : 0, C, stream_of(X)),
+     "tmgcn_mtransform_bf16");
+  return Y;
 }
 
 void check_csr(const Tensor& rowptr, const Tensor& col, const Tensor& val, const Tensor& X, int64_t N,
@@ -967,6 +994,35 @@ struct MTransformFn : public torch::autograd::Function<MTransformFn> {
   }
 };
 
+// The same with X and / or Y stored in bf16 (band operators): the backward is ONE transposed launch on the incoming
+// gradient in the dtype it arrives in, writing dX in X's dtype — bf16 dY -> fp32 dX in the model's case.
+struct MTransformBf16Fn : public torch::autograd::Function<MTransformBf16Fn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& X, const Tensor& M, int64_t band_lo, int64_t band_hi,
+                        int64_t row_off, int64_t col_off, int64_t T_out, bool out_bf16) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    ctx->save_for_backward({M});
+    ctx->saved_data["lo"] = band_lo;
+    ctx->saved_data["hi"] = band_hi;
+    ctx->saved_data["ro"] = row_off;
+    ctx->saved_data["co"] = col_off;
+    ctx->saved_data["T_in"] = X.size(0);
+    ctx->saved_data["x_bf16"] = X.scalar_type() == at::kBFloat16;
+    return mtransform_bf16(M, X, false, row_off, col_off, T_out, band_lo, band_hi, out_bf16);
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    const Tensor M = ctx->get_saved_variables()[0];
+    auto& d = ctx->saved_data;
+    const Tensor g = grads[0].contiguous();
+    const bool x_bf16 = d["x_bf16"].toBool();
+    Tensor dX = (x_bf16 || g.scalar_type() == at::kBFloat16)
+                    ? mtransform_bf16(M, g, true, d["co"].toInt(), d["ro"].toInt(), d["T_in"].toInt(), d["hi"].toInt(), d["lo"].toInt(),
+                                      x_bf16)
+                    : mtransform(M, g, true, d["co"].toInt(), d["ro"].toInt(), d["T_in"].toInt(), d["hi"].toInt(), d["lo"].toInt(), 0, 0);
+    return {dX, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
 struct SpmmFn : public torch::autograd::Function<SpmmFn> {
   // sparse.mm backward: dX_k = Â_kᵀ dY_k (Â is a constant: no gradient, as in the reference)
   static Tensor forward(AutogradContext* ctx, const Tensor& X, const Tensor& rowptr, const Tensor& col,
@@ -1449,6 +1505,10 @@ Tensor m_transform_ad(const Tensor& X, const Tensor& M, int64_t band_lo, int64_t
                       int64_t col_off, int64_t T_out, int64_t xg, int64_t yg) {
   return MTransformFn::apply(X, M, band_lo, band_hi, row_off, col_off, T_out, xg, yg);
 }
+Tensor m_transform_bf16_ad(const Tensor& X, const Tensor& M, int64_t band_lo, int64_t band_hi, int64_t row_off, int64_t col_off,
+                           int64_t T_out, bool out_bf16) {
+  return MTransformBf16Fn::apply(X, M, band_lo, band_hi, row_off, col_off, T_out, out_bf16);
+}
 Tensor spmm_ad(const Tensor& X, const Tensor& rowptr, const Tensor& col, const Tensor& val, const OptTensor& t_rowptr,
                const OptTensor& t_col, const OptTensor& t_val, int64_t N, double avg, const OptTensor& g_rows,
                const OptTensor& g_chunks, const OptTensor& t_g_rows, const OptTensor& t_g_chunks) {
@@ -1550,6 +1610,9 @@ TORCH_LIBRARY(tmgcn, m) {
         "int x_group_rows, int y_group_rows) -> Tensor");
   m.def("mtransform_out(Tensor M, Tensor X, Tensor(a!) Y, bool transpose, int row_off, int col_off, int band_lo, "
         "int band_hi, int x_group_rows, int y_group_rows) -> ()");
+  m.def("mtransform_bf16(Tensor M, Tensor X, bool transpose, int row_off, int col_off, int T_out, int band_lo, int band_hi, "
+        "bool out_bf16) -> Tensor");
+  m.def("mtransform_bf16_supported(int band_lo, int band_hi) -> bool", &mtransform_bf16_supported);
   m.def("spmm_csr_batched(Tensor rowptr, Tensor col, Tensor val, Tensor X, int N, float avg_nnz_per_row, "
         "Tensor? giant_rows=None, Tensor? giant_chunks=None) -> Tensor");
   m.def("spmm_gemm(Tensor rowptr, Tensor col, Tensor val, Tensor X, int N, Tensor W, bool trans_w, int act, "
@@ -1584,6 +1647,8 @@ TORCH_LIBRARY(tmgcn, m) {
   // differentiable
   m.def("m_transform(Tensor X, Tensor M, int band_lo, int band_hi, int row_off, int col_off, int T_out, "
         "int x_group_rows, int y_group_rows) -> Tensor");
+  m.def("m_transform_bf16(Tensor X, Tensor M, int band_lo, int band_hi, int row_off, int col_off, int T_out, "
+        "bool out_bf16) -> Tensor");
   m.def("spmm(Tensor X, Tensor rowptr, Tensor col, Tensor val, Tensor? t_rowptr, Tensor? t_col, Tensor? t_val, "
         "int N, float avg_nnz_per_row, Tensor? giant_rows=None, Tensor? giant_chunks=None, Tensor? t_giant_rows=None, "
         "Tensor? t_giant_chunks=None) -> Tensor");
@@ -1635,6 +1700,7 @@ TORCH_LIBRARY(tmgcn, m) {
 // the differentiable operators, registered alike under every key that implements them
 static void impl_differentiable(torch::Library& m) {
   m.impl("m_transform", &m_transform_ad);
+  m.impl("m_transform_bf16", &m_transform_bf16_ad);
   m.impl("spmm", &spmm_ad);
   m.impl("feature_gemm", &feature_gemm_ad);
   m.impl("spmm_feature_gemm", &spmm_feature_gemm_ad);
@@ -1656,6 +1722,7 @@ static void impl_differentiable(torch::Library& m) {
 TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("mtransform", &mtransform);
   m.impl("mtransform_out", &mtransform_out);
+  m.impl("mtransform_bf16", &mtransform_bf16);
   m.impl("spmm_csr_batched", &spmm_csr_batched);
   m.impl("spmm_gemm", &spmm_gemm);
   m.impl("spmm_gemm_out", &spmm_gemm_out);
@@ -1694,6 +1761,7 @@ TORCH_LIBRARY_IMPL(tmgcn, Autograd, m) {
 // a CPU tensor reaching a kernel-level op gets the reference-style RuntimeError, not "no kernel"
 TORCH_LIBRARY_IMPL(tmgcn, CPU, m) {
   m.impl("mtransform", &mtransform);
+  m.impl("mtransform_bf16", &mtransform_bf16);
   m.impl("spmm_csr_batched", &spmm_csr_batched);
   m.impl("spmm_gemm", &spmm_gemm);
   m.impl("bgemm", &bgemm);

@@ -395,7 +395,8 @@ class EmbeddingGCN2(_Head, _Deliver, _Sharding, nn.Module):
             raise RuntimeError(f"nonlin2 must be one of {_NONLIN}")
         # act_dtype=torch.bfloat16: the dense operand of layer 2's fused SpMM+GEMM — the layer-1 output, or its M-transform —
         # is rounded to bf16 once and gathered by the bf16 kernel (half the gathered bytes); parameters, logits and the
-        # head stay fp32.  None (default): everything as before.
+        # head stay fp32.  Where that operand is an M-transform, the transform writes it in bf16 itself and reads the
+        # gather's bf16 gradient (ops.m_transform, out_dtype).  None (default): everything as before.
         if act_dtype not in (None, torch.bfloat16):
             raise RuntimeError(f"act_dtype must be None or torch.bfloat16, got {act_dtype}")
         if act_dtype is not None:
@@ -455,10 +456,14 @@ class EmbeddingGCN2(_Head, _Deliver, _Sharding, nn.Module):
         # second layer — always the training adjacency self.At (ehf:339, 343, 348); sharded, the
         # M / M⁻¹ products below are the only steps that exchange activations between ranks
         store = ops.round_bf16 if self.act_dtype is not None else (lambda x: x)    # the gathered operand, stored in act_dtype
+        # act_dtype: the M product writes the bf16 operand itself and its backward reads the gather's bf16 gradient (one
+        # launch each way, ops.m_transform; act_dtype refuses group=, so this is never the sharded exchange)
+        mt_store = (lambda y: ops.m_transform(y, self.Mop, out_dtype=self.act_dtype)) if self.act_dtype is not None \
+            else (lambda y: self._mt(y, self.Mop))
         if self.use_Minv:
-            Z = self._mt(ops.spmm_feature_gemm(self.At, store(self._mt(Y, self.Mop)), W2), self.Minv)
+            Z = self._mt(ops.spmm_feature_gemm(self.At, mt_store(Y), W2), self.Minv)
         elif self.apply_M_twice:
-            Z = ops.spmm_feature_gemm(self.At, store(self._mt(Y, self.Mop)), W2)
+            Z = ops.spmm_feature_gemm(self.At, mt_store(Y), W2)
             if self.apply_M_three_times:
                 Z = self._mt(Z, self.Mop)                                          # ehf:346
         else:

@@ -290,10 +290,22 @@ class HipKernels:
 
     # P1 ---------------------------------------------------------------------------------
     def mtransform(self, op: MOperator, X: torch.Tensor, transpose=False, row_off=0, col_off=0,
-                   T_out: Optional[int] = None, x_group_rows=0, y_group_rows=0) -> torch.Tensor:
+                   T_out: Optional[int] = None, x_group_rows=0, y_group_rows=0, out_dtype=None) -> torch.Tensor:
+        """One launch of the M (or Mᵀ) product.  An fp32 X with out_dtype None / fp32 is tmgcn_mtransform_f32; an X stored
+        in bf16 and / or out_dtype=torch.bfloat16 is the band kernel of csrc/mtransform_bf16.hip (operators of at most 20
+        diagonals, plain row order; timer tags mtransform_bf16 / mtransform_bf16_T)."""
         lo, hi = (op.band_hi, op.band_lo) if transpose else (op.band_lo, op.band_hi)
+        y_bf16 = _y_bf16(out_dtype)
+        if X.dtype == torch.bfloat16 or y_bf16:
+            if x_group_rows or y_group_rows:
+                raise RuntimeError("x_group_rows / y_group_rows are not available with a bf16-stored operand")
+            return self._run("mtransform_bf16_T" if transpose else "mtransform_bf16", X.device, lambda: self.ops.mtransform_bf16(
+                op.M, X, bool(transpose), row_off, col_off, -1 if T_out is None else T_out, lo, hi, y_bf16))
         return self._run("mtransform_T" if transpose else "mtransform", X.device, lambda: self.ops.mtransform(
             op.M, X, bool(transpose), row_off, col_off, -1 if T_out is None else T_out, lo, hi, x_group_rows, y_group_rows))
+
+    def mtransform_bf16_supported(self, band_lo: int, band_hi: int) -> bool:
+        return bool(_lib.load().tmgcn_mtransform_bf16_supported(band_lo, band_hi))
 
     def mtransform_out(self, op: MOperator, X: torch.Tensor, Y: torch.Tensor, transpose=False, row_off=0, col_off=0,
                        x_group_rows=0, y_group_rows=0, tag=None) -> torch.Tensor:
@@ -401,6 +413,20 @@ class _MTransform(torch.autograd.Function):
         dX = kernels.mtransform(ctx.op, dY.contiguous(), True, ctx.col_off, ctx.row_off, ctx.T_in,
                                 x_group_rows=ctx.yg, y_group_rows=ctx.xg)
         return dX, None, None, None, None, None, None
+
+
+class _MTransformBf16(torch.autograd.Function):
+    """_MTransform with X and / or Y stored in bf16: one fused launch each way, dX in X's dtype."""
+
+    @staticmethod
+    def forward(ctx, X, op, row_off, col_off, T_out, out_dtype):
+        ctx.op, ctx.row_off, ctx.col_off, ctx.T_in, ctx.x_dtype = op, row_off, col_off, X.shape[0], X.dtype
+        return kernels.mtransform(op, X, False, row_off, col_off, T_out, out_dtype=out_dtype)
+
+    @staticmethod
+    def backward(ctx, dY):
+        dX = kernels.mtransform(ctx.op, dY.contiguous(), True, ctx.col_off, ctx.row_off, ctx.T_in, out_dtype=ctx.x_dtype)
+        return dX, None, None, None, None, None
 
 
 class _Spmm(torch.autograd.Function):
@@ -525,14 +551,40 @@ def _giant(A: BatchedCSR, needed: bool):
     return (*A.giant_plan(), *(A.transpose().giant_plan() if needed else (None, None)))
 
 
+def m_transform_bf16_fused(op: MOperator) -> bool:
+    """True when m_transform on a bf16-stored operand (a bf16 X and / or out_dtype=torch.bfloat16) is ONE launch each way
+    (csrc/mtransform_bf16.hip: band operators of at most 20 diagonals, both for M and for Mᵀ); False when it is the fp32
+    transform between cast launches (Minv, dense M)."""
+    return kernels.name == "hip" and kernels.mtransform_bf16_supported(int(op.band_lo), int(op.band_hi))
+
+
 def m_transform(X: torch.Tensor, op: MOperator, row_off=0, col_off=0, T_out=None, x_group_rows=0,
-                y_group_rows=0) -> torch.Tensor:
+                y_group_rows=0, out_dtype=None) -> torch.Tensor:
     """P1: Y[k] = Σ_j M[row_off+k][col_off+j] · X[j]  along the first (time) mode.
-    x_group_rows / y_group_rows: group-interleaved row storage of X / Y (include/tmgcn.h)."""
-    if _registered():
-        return kernels.ops.m_transform(X, op.M, op.band_lo, op.band_hi, row_off, col_off,
-                                       -1 if T_out is None else T_out, x_group_rows, y_group_rows)
-    return _MTransform.apply(X, op, row_off, col_off, T_out, x_group_rows, y_group_rows)
+    x_group_rows / y_group_rows: group-interleaved row storage of X / Y (include/tmgcn.h).
+
+    X may be stored in bf16, and out_dtype=torch.bfloat16 (None / torch.float32: fp32) stores Y in bf16.  The value is
+    always the fp32 transform of the widened X, rounded to nearest even once where Y is bf16; the gradient of X comes back
+    in X's dtype.  With a band operator (m_transform_bf16_fused(op)) that is one launch each way, the cast folded into the
+    kernel's load / store: 6 B per element instead of 14.  With a dense operator (Minv, more than 20 diagonals) the call
+    composes the fp32 transform with the existing cast launches — the same bits, nothing saved.  Grouped rows are not
+    available with a bf16-stored operand."""
+    y_bf16 = _y_bf16(out_dtype)
+    if X.dtype != torch.bfloat16 and not y_bf16:
+        if _registered():
+            return kernels.ops.m_transform(X, op.M, op.band_lo, op.band_hi, row_off, col_off,
+                                           -1 if T_out is None else T_out, x_group_rows, y_group_rows)
+        return _MTransform.apply(X, op, row_off, col_off, T_out, x_group_rows, y_group_rows)
+    if x_group_rows or y_group_rows:
+        raise RuntimeError(f"x_group_rows={x_group_rows} / y_group_rows={y_group_rows} are not available with a bf16-stored "
+                           "operand (the sharded layer exchanges fp32 activations)")
+    if m_transform_bf16_fused(op):
+        if _registered():
+            return kernels.ops.m_transform_bf16(X, op.M, op.band_lo, op.band_hi, row_off, col_off,
+                                                -1 if T_out is None else T_out, y_bf16)
+        return _MTransformBf16.apply(X, op, row_off, col_off, T_out, torch.bfloat16 if y_bf16 else torch.float32)
+    Y = m_transform(kernels.ops.widen_params([X])[0] if X.dtype == torch.bfloat16 else X, op, row_off, col_off, T_out)
+    return round_bf16(Y) if y_bf16 else Y
 
 
 def spmm(A: BatchedCSR, X: torch.Tensor) -> torch.Tensor:
