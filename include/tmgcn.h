@@ -288,6 +288,36 @@ int tmgcn_gemm_dw_act_f32(const float* A, const float* dY, const float* pre_act,
                           int64_t R, int32_t K, int32_t Nf, int64_t rows_per_batch,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- P3 of layer 1 on the bf16 activation path: Y stored in bf16, dW from a bf16 dY ----------------
+ * Replaces  Y = nonlin(t.matmul(AtXt, W1))  (ehf:330-334) and autograd's weight gradient of it where the layer-1 output
+ * is STORED in bf16 for the gather of layer 2 (EmbeddingGCN2(act_dtype=bfloat16), default branch, ehf:348-349): with the
+ * fp32 entries that is tmgcn_gemm_f32 + a cast launch forward (4K + 14F bytes per row, an fp32 [T,N,F] temporary) and a
+ * widening launch + tmgcn_act_bwd_f32 + tmgcn_gemm_dw_f32 backward (4K + 22F); here each direction is one launch over
+ * 4K + 6F bytes per row.
+ *   tmgcn_gemm_bf16y        Y_bf16[r][n] = rne_bf16( act( sum_k A[r][k] * W_b[k][n] ) ), A, W and pre_act fp32, trans_w = 0;
+ *                           R, K, Nf, rows_per_batch, w_batch_stride, act, pre_act as in tmgcn_gemm_f32.  The fp32 sum is
+ *                           that entry's (TMGCN_GEMM_AUTO), so Y_bf16 is bit for bit its Y rounded to nearest even once and
+ *                           pre_act is bit for bit its pre_act.
+ *   tmgcn_gemm_dw_act_bf16  dW_b = A_bᵀ · (widen(dY_bf16) ⊙ act'(pre_act)): dY as bf16 bit patterns, widened exactly; the
+ *                           product with act' one rounded fp32 multiply, i.e. the value tmgcn_act_bwd_f32 stores, so dW is bit
+ *                           for bit tmgcn_gemm_dw_f32 (TMGCN_DW_AUTO) on that tensor.  act = TMGCN_ACT_NONE: pre_act is not
+ *                           read (may be NULL).  Workspace: tmgcn_gemm_dw_workspace_bytes(), as tmgcn_gemm_dw_f32.
+ * Both on tmgcn_gemm_bf16y_supported(K, Nf) != 0 only: Nf a multiple of 8 in [16, 128] (the K of the bf16 gather that reads
+ * Y) and either K a multiple of 4 in [16, 128] (the bf16-split matrix-core kernels) or 1 <= K < 16 with Nf <= 64 (the
+ * thread-per-row kernels).  Not covered (0): K > 128 (k-chunked), the exact-f32 MFMA route, any other K.
+ * TMGCN_ERR_INVALID, and no launch, on: a bad shape, act out of range, unsupported K / Nf, a NULL A / W / Y / dY / dW, pre_act
+ * NULL with act != NONE (dW entry), A not 16-byte aligned (4-byte where K < 16), Y / dY not 2-byte aligned (dY: 8-byte for
+ * K >= 16), W / dW / pre_act not 4-byte aligned (the dW entry's pre_act: 16-byte for K >= 16).  TMGCN_ERR_WORKSPACE, and no
+ * launch, on a workspace that is NULL or too small.  TMGCN_OK without a launch when R == 0 (dW is then left untouched).
+ * No atomics: the same bits on every run. */
+int tmgcn_gemm_bf16y_supported(int32_t K, int32_t Nf);
+int tmgcn_gemm_bf16y(const float* A, const float* W, uint16_t* Y_bf16, float* pre_act,
+                     int64_t R, int32_t K, int32_t Nf, int64_t rows_per_batch, int64_t w_batch_stride,
+                     int32_t act, void* stream);
+int tmgcn_gemm_dw_act_bf16(const float* A, const uint16_t* dY_bf16, const float* pre_act, int32_t act, float* dW,
+                           int64_t R, int32_t K, int32_t Nf, int64_t rows_per_batch,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- layers 1 + 2 of the narrow 2-layer models, fused (ABI 4) --------------------------------------
  *   forward   Z = act2( (Â ⋆ act1(H·W1)) · W2 )     ehf:330-335 + 348-349 (EmbeddingGCN2, default branch), ehf:486-487 (KWGCN)
  *   backward  dW1 = Σ_r H[r]ᵀ · ( ((Âᵀ ⋆ dZ')·W2ᵀ)[r] ⊙ act1'(H[r]·W1) ),   dZ' = dZ ⊙ act2'(pre2)

@@ -53,6 +53,9 @@ SIGNATURES = {
     "tmgcn_gemm_dw_f32": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i64, _i32, _p, _i64, _p]),
     "tmgcn_gemm_dw_act_supported": (C.c_int, [_i32, _i32]),
     "tmgcn_gemm_dw_act_f32": (C.c_int, [_p, _p, _p, _i32, _p, _i64, _i32, _i32, _i64, _p, _i64, _p]),
+    "tmgcn_gemm_bf16y_supported": (C.c_int, [_i32, _i32]),
+    "tmgcn_gemm_bf16y": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i64, _i64, _i32, _p]),
+    "tmgcn_gemm_dw_act_bf16": (C.c_int, [_p, _p, _p, _i32, _p, _i64, _i32, _i32, _i64, _p, _i64, _p]),
     "tmgcn_layer12_supported": (C.c_int, [_i32, _i32, _i32]),
     "tmgcn_layer12_fwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _i32, _p, _i32, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, C.c_float, _p, _i32, _p]),
     "tmgcn_layer12_fwd_pays": (C.c_int, [_i64, _i32, _i32, C.c_float]),

@@ -178,6 +178,16 @@ inline int allow_large_lds(K kernel, size_t bytes, const char* what) {
   return TMGCN_OK;
 }
 
+typedef uint16_t bf16_t;  // a bf16 bit pattern: the upper half of an fp32
+
+// fp32 -> bf16 bits, round to nearest even: the rounding of st_elem (pointwise.hip), i.e. of the cast launch that the
+// kernels storing bf16 themselves replace (mtransform_band.h, the bf16-Y forms of gemm.hip)
+__device__ __forceinline__ unsigned bf16_rne_bits(float v) {
+  unsigned u = __float_as_uint(v);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+
 // 4x4 transpose across a lane quad: on entry register k of lane j (j = lane & 3) holds M[k][j], on
 // exit it holds M[j][k].  The MFMA accumulator layout has the output COLUMN on the lane and four
 // consecutive ROWS in consecutive registers, so a plain epilogue stores one dword per lane per row

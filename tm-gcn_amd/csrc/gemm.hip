@@ -215,9 +215,15 @@ struct GxTile {
 // row = (i&3) + 8*(i>>2) + 4*(lane>>5).  One 64-bit base per lane and 32-bit row offsets; whole
 // tiles take the branch-free path.
 // ADD: the tile is one k-chunk's contribution — add what Y already holds before the activation
-template <int ACT, bool ADD = false>
-__device__ __forceinline__ void gx_store_rows(const f32x16 (&acc)[2], float* yb, float* pb, int Nf, int tile_rows,
+// YT: how Y is stored — float, or bf16_t: the activated fp32 value rounded to nearest even once (gx_y_store), i.e. the
+// bits of the cast launch on the fp32 launch's Y; pre stays fp32
+__device__ __forceinline__ void gx_y_store(float* p, float v) { *p = v; }
+__device__ __forceinline__ void gx_y_store(bf16_t* p, float v) { *p = (bf16_t)bf16_rne_bits(v); }
+
+template <int ACT, bool ADD = false, class YT = float>
+__device__ __forceinline__ void gx_store_rows(const f32x16 (&acc)[2], YT* yb, float* pb, int Nf, int tile_rows,
                                               int rows_left) {
+  static_assert(!ADD || std::is_same<YT, float>::value, "k-chunks accumulate in an fp32 Y");
   if (tile_rows == BM) {
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
@@ -227,7 +233,7 @@ __device__ __forceinline__ void gx_store_rows(const f32x16 (&acc)[2], float* yb,
         float sv = acc[mb][i];
         if (ADD) sv += yb[off];
         if (pb) pb[off] = sv;
-        yb[off] = act_apply(sv, ACT);
+        gx_y_store(yb + off, act_apply(sv, ACT));
       }
   } else {
 #pragma unroll
@@ -239,7 +245,7 @@ __device__ __forceinline__ void gx_store_rows(const f32x16 (&acc)[2], float* yb,
           float sv = acc[mb][i];
           if (ADD) sv += yb[rr * Nf];
           if (pb) pb[rr * Nf] = sv;
-          yb[rr * Nf] = act_apply(sv, ACT);
+          gx_y_store(yb + rr * Nf, act_apply(sv, ACT));
         }
       }
   }
@@ -249,9 +255,11 @@ __device__ __forceinline__ void gx_store_rows(const f32x16 (&acc)[2], float* yb,
 // quad) is transposed in registers (quad_transpose4), after which lane j of a quad owns row j and
 // columns 4q..4q+3.  y0 / p0 point at (tile row 0, this wave's column strip); needs Nf % 4 == 0 and
 // 16-byte aligned outputs (checked by the caller).  Rows past the tile's end are predicated off.
-template <int ACT, bool ADD = false>
-__device__ __forceinline__ void gx_store_rows_v4(const f32x16 (&acc)[2], float* y0, float* p0, int Nf, int rows,
+// A bf16 Y leaves as 4 bf16 = 8 bytes per lane (8-byte aligned Y).
+template <int ACT, bool ADD = false, class YT = float>
+__device__ __forceinline__ void gx_store_rows_v4(const f32x16 (&acc)[2], YT* y0, float* p0, int Nf, int rows,
                                                  int li, int lh, bool cols_ok) {
+  static_assert(!ADD || std::is_same<YT, float>::value, "k-chunks accumulate in an fp32 Y");
   // opaque copies: otherwise the eight row offsets and row tests are hoisted out of the tile loop as
   // loop invariants and pinned in registers for the whole kernel, beside the 96-VGPR operator strip
   asm volatile("" : "+v"(li), "+v"(lh));
@@ -265,7 +273,7 @@ __device__ __forceinline__ void gx_store_rows_v4(const f32x16 (&acc)[2], float* 
       const int rr = mb * 32 + 8 * g + 4 * lh + j;
       if (rr < rows && cols_ok) {
         const int off = rr * Nf + 4 * q;
-        if (ADD) {
+        if constexpr (ADD) {
           const float4 old = *reinterpret_cast<const float4*>(y0 + off);
           v[0] += old.x;
           v[1] += old.y;
@@ -273,8 +281,13 @@ __device__ __forceinline__ void gx_store_rows_v4(const f32x16 (&acc)[2], float* 
           v[3] += old.w;
         }
         if (p0) *reinterpret_cast<float4*>(p0 + off) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4*>(y0 + off) =
-            make_float4(act_apply(v[0], ACT), act_apply(v[1], ACT), act_apply(v[2], ACT), act_apply(v[3], ACT));
+        if constexpr (std::is_same<YT, float>::value)
+          *reinterpret_cast<float4*>(y0 + off) =
+              make_float4(act_apply(v[0], ACT), act_apply(v[1], ACT), act_apply(v[2], ACT), act_apply(v[3], ACT));
+        else
+          *reinterpret_cast<uint2*>(y0 + off) =
+              make_uint2(bf16_rne_bits(act_apply(v[0], ACT)) | (bf16_rne_bits(act_apply(v[1], ACT)) << 16),
+                         bf16_rne_bits(act_apply(v[2], ACT)) | (bf16_rne_bits(act_apply(v[3], ACT)) << 16));
       }
       __builtin_amdgcn_sched_barrier(0);  // one 4x4 block in flight: the B strip leaves ~60 VGPRs for everything else
     }
@@ -286,8 +299,11 @@ __device__ __forceinline__ void gx_store_rows_v4(const f32x16 (&acc)[2], float* 
 // its fp32-widened copy at half the matrix-core work.
 // CH = the launch is one k-chunk of a product wider than 128 (see GemmArgs::lda): the non-chunked
 // instantiations compile to exactly the code they had before the chunked form existed.
-template <int WP, bool CH = false>
+// YT = bf16_t: a.Y points at bf16 elements (tmgcn_gemm_bf16y: the layer-1 output of the bf16 activation path, stored as
+// the gather reads it); only the two epilogues differ, so every fp32-Y instantiation is the code it was.
+template <int WP, bool CH = false, class YT = float>
 __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmArgs a) {
+  static_assert(std::is_same<YT, float>::value || !CH, "a bf16 Y has no k-chunked form");
   __shared__ __attribute__((aligned(16))) unsigned char sm[3 * GX_PLANE];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -483,14 +499,15 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmArgs a) {
         if (ks < nks) k_step(ks);
     }
   };
-  // 16-byte stores need whole column quads inside Nf and aligned rows
-  const bool v4 = (a.Nf % 4 == 0) && (reinterpret_cast<uintptr_t>(a.Y) % 16 == 0) &&
+  // 16-byte stores (8-byte ones of a bf16 Y) need whole column quads inside Nf and aligned rows
+  YT* const Yp = reinterpret_cast<YT*>(a.Y);
+  const bool v4 = (a.Nf % 4 == 0) && (reinterpret_cast<uintptr_t>(a.Y) % (4 * sizeof(YT)) == 0) &&
                   (!a.pre || reinterpret_cast<uintptr_t>(a.pre) % 16 == 0);
   auto store_tile = [&](const GxTile& tc) __attribute__((always_inline)) {
     if (!strip) return;
     if (v4) {  // every lane takes part in the quad transposes; columns past Nf are predicated off
       const int64_t base = tc.row0 * a.Nf + n0;
-      float* y0 = a.Y + base;
+      YT* y0 = Yp + base;
       float* p0 = a.pre ? a.pre + base : nullptr;
       const bool cols_ok = n0 + 4 * (li >> 2) < a.Nf;
       if constexpr (CH) {
@@ -505,17 +522,17 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmArgs a) {
         }
       }
       switch (a.act) {
-        case TMGCN_ACT_RELU: gx_store_rows_v4<TMGCN_ACT_RELU>(acc, y0, p0, a.Nf, tc.rows, li, lh, cols_ok); break;
-        case TMGCN_ACT_LEAKY: gx_store_rows_v4<TMGCN_ACT_LEAKY>(acc, y0, p0, a.Nf, tc.rows, li, lh, cols_ok); break;
-        case TMGCN_ACT_SELU: gx_store_rows_v4<TMGCN_ACT_SELU>(acc, y0, p0, a.Nf, tc.rows, li, lh, cols_ok); break;
-        default: gx_store_rows_v4<TMGCN_ACT_NONE>(acc, y0, p0, a.Nf, tc.rows, li, lh, cols_ok);
+        case TMGCN_ACT_RELU: gx_store_rows_v4<TMGCN_ACT_RELU, false, YT>(acc, y0, p0, a.Nf, tc.rows, li, lh, cols_ok); break;
+        case TMGCN_ACT_LEAKY: gx_store_rows_v4<TMGCN_ACT_LEAKY, false, YT>(acc, y0, p0, a.Nf, tc.rows, li, lh, cols_ok); break;
+        case TMGCN_ACT_SELU: gx_store_rows_v4<TMGCN_ACT_SELU, false, YT>(acc, y0, p0, a.Nf, tc.rows, li, lh, cols_ok); break;
+        default: gx_store_rows_v4<TMGCN_ACT_NONE, false, YT>(acc, y0, p0, a.Nf, tc.rows, li, lh, cols_ok);
       }
       return;
     }
     const int n = n0 + li;
     if (n >= a.Nf) return;
     const int64_t base = (tc.row0 + 4 * lh) * a.Nf + n;
-    float* yb = a.Y + base;
+    YT* yb = Yp + base;
     float* pb = a.pre ? a.pre + base : nullptr;
     const int rows_left = tc.rows - 4 * lh;
     if constexpr (CH) {
@@ -530,10 +547,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmArgs a) {
       }
     }
     switch (a.act) {  // chosen once per tile, not once per element
-      case TMGCN_ACT_RELU: gx_store_rows<TMGCN_ACT_RELU>(acc, yb, pb, a.Nf, tc.rows, rows_left); break;
-      case TMGCN_ACT_LEAKY: gx_store_rows<TMGCN_ACT_LEAKY>(acc, yb, pb, a.Nf, tc.rows, rows_left); break;
-      case TMGCN_ACT_SELU: gx_store_rows<TMGCN_ACT_SELU>(acc, yb, pb, a.Nf, tc.rows, rows_left); break;
-      default: gx_store_rows<TMGCN_ACT_NONE>(acc, yb, pb, a.Nf, tc.rows, rows_left);
+      case TMGCN_ACT_RELU: gx_store_rows<TMGCN_ACT_RELU, false, YT>(acc, yb, pb, a.Nf, tc.rows, rows_left); break;
+      case TMGCN_ACT_LEAKY: gx_store_rows<TMGCN_ACT_LEAKY, false, YT>(acc, yb, pb, a.Nf, tc.rows, rows_left); break;
+      case TMGCN_ACT_SELU: gx_store_rows<TMGCN_ACT_SELU, false, YT>(acc, yb, pb, a.Nf, tc.rows, rows_left); break;
+      default: gx_store_rows<TMGCN_ACT_NONE, false, YT>(acc, yb, pb, a.Nf, tc.rows, rows_left);
     }
   };
 
@@ -581,6 +598,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(GemmArgs a) {
 // With stage_off the block's 256 x Nf outputs go through an LDS tile and leave as one contiguous,
 // fully coalesced stream (a row is Nf*4 bytes: stored lane by lane it is Nf dword stores at that
 // stride per wave — 21 us for 570 k rows of 2 -> 6 with the pre-activation, against 8 us of bytes).
+// YT = bf16_t: Y stored in bf16 (as in gemm_bf16x3_kernel), from either exit.
+template <class YT = float>
 __global__ __launch_bounds__(256) void gemm_small_kernel(GemmArgs a) {
   extern __shared__ float Ws[];  // [n_w][K][Nfp] (+ [256][Nfp+1] output tile at stage_off)
   const ActApply act(a.act);    // decoded once: no switch per element (common.h)
@@ -600,6 +619,7 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(GemmArgs a) {
   const int64_t r = r_first + threadIdx.x;
   const bool live = r < a.R;
   float* tile = a.stage_off ? Ws + a.stage_off + threadIdx.x * (Nfp + 1) : nullptr;
+  YT* const Yp = reinterpret_cast<YT*>(a.Y);
   if (live) {
     const float* Wl = Ws + (int64_t)(r / batch_rows - b_first) * a.K * Nfp;
     const float* Ar = a.A + r * a.K;
@@ -621,7 +641,7 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(GemmArgs a) {
         for (int i = 0; i < 8; ++i) {
           if (nb + i < a.Nf) {
             if (a.pre) a.pre[r * a.Nf + nb + i] = acc[i];
-            a.Y[r * a.Nf + nb + i] = act(acc[i]);
+            gx_y_store(Yp + r * a.Nf + nb + i, act(acc[i]));
           }
         }
       }
@@ -631,13 +651,13 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(GemmArgs a) {
   __syncthreads();
   const float* t0 = Ws + a.stage_off;
   const int total = (int)(r_last - r_first + 1) * a.Nf;
-  float* yb = a.Y + r_first * a.Nf;
+  YT* yb = Yp + r_first * a.Nf;
   float* pb = a.pre ? a.pre + r_first * a.Nf : nullptr;
   for (int idx = threadIdx.x; idx < total; idx += 256) {
     const int row = idx / a.Nf, n = idx - row * a.Nf;
     const float v = t0[row * (Nfp + 1) + n];
     if (pb) pb[idx] = v;
-    yb[idx] = act(v);
+    gx_y_store(yb + idx, act(v));
   }
 }
 
@@ -842,6 +862,27 @@ constexpr int X3_OPERAND = 3 * X3_PLANE;
 
 __device__ __forceinline__ float comp(const float4& v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 
+// How the dW kernels receive dY (tmgcn_gemm_dw_act_bf16: the layer-1 weight gradient of the bf16 activation path, whose
+// incoming gradient is the bf16 dX of the layer-2 gather):
+//   DY_F32       fp32, as it is
+//   DY_BF16      bf16 bit patterns (a.dY points at bf16_t), widened exactly
+//   DY_BF16_ACT  the same, times act'(pre) (a.pre fp32, a.act): one rounded fp32 multiply per element — __fmul_rn, so that
+//                the compiler cannot contract it into the first subtraction of split3 — which is the value that
+//                tmgcn_act_bwd_f32 stores for the fp32 kernel to read: the same operand bits, hence the same dW bits
+enum { DY_F32 = 0, DY_BF16 = 1, DY_BF16_ACT = 2 };
+
+// four bf16 (8 bytes) -> the float4 they widen to, times g (act' of the same four elements)
+__device__ __forceinline__ float4 dy_widen(const uint2 u) {
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                     __uint_as_float(u.y & 0xffff0000u));
+}
+__device__ __forceinline__ float4 dy_widen_act(const uint2 u, const float4& pre, const ActGrad& dact) {
+  const float4 d = dy_widen(u);
+  return make_float4(__fmul_rn(d.x, dact(pre.x)), __fmul_rn(d.y, dact(pre.y)), __fmul_rn(d.z, dact(pre.z)),
+                     __fmul_rn(d.w, dact(pre.w)));
+}
+
+template <int DYM = DY_F32>
 __global__ __launch_bounds__(256, X3_OCC) void gemm_dw_bf16x3_kernel(DwArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sm[2 * X3_OPERAND];
   const int lane = threadIdx.x & 63;
@@ -868,35 +909,61 @@ __global__ __launch_bounds__(256, X3_OCC) void gemm_dw_bf16x3_kernel(DwArgs a) {
   // has no conditional load (those force s_waitcnt vmcnt(0) and exec-mask branches)
   const bool okA = kbase + 4 * fq < a.K, okB = nbase + 4 * fq < a.Nf;
   const float* pa = a.A + (r0 + 4 * kg) * a.K + (okA ? kbase + 4 * fq : 0);
-  const float* pb = a.dY + (r0 + 4 * kg) * a.Nf + (okB ? nbase + 4 * fq : 0);
+  using DyE = typename std::conditional<DYM == DY_F32, float, bf16_t>::type;   // an element of dY in memory
+  using DyQ = typename std::conditional<DYM == DY_F32, float4, uint2>::type;   // a staged quad of it
+  constexpr int NPRE = DYM == DY_BF16_ACT ? X3_DEPTH : 0;                      // staging sets of pre quads
+  const DyE* pb = reinterpret_cast<const DyE*>(a.dY) + (r0 + 4 * kg) * a.Nf + (okB ? nbase + 4 * fq : 0);
+  const float* pp = DYM == DY_BF16_ACT ? a.pre + (r0 + 4 * kg) * a.Nf + (okB ? nbase + 4 * fq : 0) : nullptr;
+  const ActGrad dact(DYM == DY_BF16_ACT ? a.act : 0);
   const float za = okA ? 1.f : 0.f, zb = okB ? 1.f : 0.f;
   // X3_DEPTH staging sets form a ring: the rows of step n+DEPTH are requested as soon as step n has
   // been split, so a request has DEPTH whole steps to arrive.  The ring loop contains no conditional
   // load (the compiler then counts outstanding loads exactly: s_waitcnt vmcnt(8*(DEPTH-1)) instead of
   // draining every request before each split); chunk heads/tails go through the plain loop below.
-  float4 sa[X3_DEPTH][4], sb[X3_DEPTH][4];
-  auto fetch_full = [&](float4 (&xa)[4], float4 (&xb)[4]) {
+  // A bf16 dY is staged as it is loaded (8 bytes per quad, beside the fp32 pre quad where act' applies) and turned into
+  // the fp32 operand only when it is split (dy_quads): the loads stay unconditional and in flight for a whole step.
+  float4 sa[X3_DEPTH][4];
+  DyQ sb[X3_DEPTH][4];
+  float4 sp[NPRE ? NPRE : 1][4];
+  auto fetch_full = [&](float4 (&xa)[4], DyQ (&xb)[4], float4 (&xp)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       xa[i] = *reinterpret_cast<const float4*>(pa + (int64_t)i * a.K);
-      xb[i] = *reinterpret_cast<const float4*>(pb + (int64_t)i * a.Nf);
+      xb[i] = *reinterpret_cast<const DyQ*>(pb + (int64_t)i * a.Nf);
+      if constexpr (DYM == DY_BF16_ACT) xp[i] = *reinterpret_cast<const float4*>(pp + (int64_t)i * a.Nf);
     }
     pa += (int64_t)X3_ROWS * a.K;
     pb += (int64_t)X3_ROWS * a.Nf;
+    if constexpr (DYM == DY_BF16_ACT) pp += (int64_t)X3_ROWS * a.Nf;
   };
-  auto fetch_any = [&](float4 (&xa)[4], float4 (&xb)[4], int64_t r) {  // r < r1; rows past r1 read row r1-1 and are zeroed
+  // the fp32 dY operand of a staged set: the quads themselves, or their widening (times act'(pre))
+  auto dy_quads = [&](const DyQ (&xb)[4], const float4 (&xp)[4], float4 (&g)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if constexpr (DYM == DY_F32) g[i] = xb[i];
+      else if constexpr (DYM == DY_BF16) g[i] = dy_widen(xb[i]);
+      else g[i] = dy_widen_act(xb[i], xp[i], dact);
+    }
+  };
+  // r < r1; rows past r1 read row r1-1 (dY and pre of the SAME row) and are zeroed; xb receives the fp32 operand
+  auto fetch_any = [&](float4 (&xa)[4], float4 (&xb)[4], int64_t r) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int64_t row = r + 4 * kg + i;
       const int64_t back = row < r1 ? 0 : row - (r1 - 1);
       const float z = row < r1 ? 1.f : 0.f;
       const float4 va = *reinterpret_cast<const float4*>(pa + ((int64_t)i - back) * a.K);
-      const float4 vb = *reinterpret_cast<const float4*>(pb + ((int64_t)i - back) * a.Nf);
+      float4 vb;
+      if constexpr (DYM == DY_F32) vb = *reinterpret_cast<const float4*>(pb + ((int64_t)i - back) * a.Nf);
+      else if constexpr (DYM == DY_BF16) vb = dy_widen(*reinterpret_cast<const uint2*>(pb + ((int64_t)i - back) * a.Nf));
+      else vb = dy_widen_act(*reinterpret_cast<const uint2*>(pb + ((int64_t)i - back) * a.Nf),
+                             *reinterpret_cast<const float4*>(pp + ((int64_t)i - back) * a.Nf), dact);
       xa[i] = make_float4(va.x * z, va.y * z, va.z * z, va.w * z);
       xb[i] = make_float4(vb.x * z, vb.y * z, vb.z * z, vb.w * z);
     }
     pa += (int64_t)X3_ROWS * a.K;
     pb += (int64_t)X3_ROWS * a.Nf;
+    if constexpr (DYM == DY_BF16_ACT) pp += (int64_t)X3_ROWS * a.Nf;
   };
 
   f32x16 acc[4], sum[4];
@@ -983,13 +1050,19 @@ __global__ __launch_bounds__(256, X3_OCC) void gemm_dw_bf16x3_kernel(DwArgs a) {
   const int64_t full_end = r0 + ((r1 - r0) / X3_ROWS) * X3_ROWS;  // end of the whole steps
   if (full_end - r0 >= 2 * X3_DEPTH * X3_ROWS) {
 #pragma unroll
-    for (int d = 0; d < X3_DEPTH; ++d) fetch_full(sa[d], sb[d]);
+    for (int d = 0; d < X3_DEPTH; ++d) fetch_full(sa[d], sb[d], sp[NPRE ? d : 0]);
     for (; r + 2 * X3_DEPTH * X3_ROWS <= full_end; r += X3_DEPTH * X3_ROWS) {
 #pragma unroll
       for (int d = 0; d < X3_DEPTH; ++d) {
         __syncthreads();  // the previous step's fragments have been read
-        split_store(sa[d], sb[d]);
-        fetch_full(sa[d], sb[d]);  // refill this set for step +DEPTH
+        if constexpr (DYM == DY_F32) {
+          split_store(sa[d], sb[d]);
+        } else {
+          float4 g[4];
+          dy_quads(sb[d], sp[NPRE ? d : 0], g);
+          split_store(sa[d], g);
+        }
+        fetch_full(sa[d], sb[d], sp[NPRE ? d : 0]);  // refill this set for step +DEPTH
         __syncthreads();
         multiply();
       }
@@ -997,16 +1070,29 @@ __global__ __launch_bounds__(256, X3_OCC) void gemm_dw_bf16x3_kernel(DwArgs a) {
 #pragma unroll
     for (int d = 0; d < X3_DEPTH; ++d) {  // drain the ring
       __syncthreads();
-      split_store(sa[d], sb[d]);
+      if constexpr (DYM == DY_F32) {
+        split_store(sa[d], sb[d]);
+      } else {
+        float4 g[4];
+        dy_quads(sb[d], sp[NPRE ? d : 0], g);
+        split_store(sa[d], g);
+      }
       __syncthreads();
       multiply();
     }
     r += X3_DEPTH * X3_ROWS;
   }
   for (; r < r1; r += X3_ROWS) {  // what is left of the chunk (and chunks too short for the ring)
-    fetch_any(sa[0], sb[0], r);
-    __syncthreads();
-    split_store(sa[0], sb[0]);
+    if constexpr (DYM == DY_F32) {
+      fetch_any(sa[0], sb[0], r);
+      __syncthreads();
+      split_store(sa[0], sb[0]);
+    } else {
+      float4 g[4];
+      fetch_any(sa[0], g, r);
+      __syncthreads();
+      split_store(sa[0], g);
+    }
     __syncthreads();
     multiply();
   }
@@ -1040,7 +1126,9 @@ __global__ __launch_bounds__(256, X3_OCC) void gemm_dw_bf16x3_kernel(DwArgs a) {
 // reference's 2x6 / 6x6) the 256 threads form 256/(K*Nf) row groups that each take every g-th row
 // of the tile, so all lanes work; with more outputs each thread owns up to 4 output elements.
 // fp64 running sums (free at these sizes), groups combined through LDS in fixed order.
+// DYM: dY as fp32, or as bf16 widened (and multiplied by act'(pre)) while it is staged into sd — see DY_F32 above.
 constexpr int DW_ROWS = 64;
+template <int DYM = DY_F32>
 __global__ __launch_bounds__(256) void gemm_dw_small_kernel(DwArgs a) {
   extern __shared__ float sm[];  // [DW_ROWS][K] then [DW_ROWS][Nf]
   __shared__ double red[256];
@@ -1071,7 +1159,16 @@ __global__ __launch_bounds__(256) void gemm_dw_small_kernel(DwArgs a) {
     const int nr = (int)((r1 - r) < DW_ROWS ? (r1 - r) : DW_ROWS);
     __syncthreads();
     for (int t = threadIdx.x; t < nr * a.K; t += 256) sa[t] = a.A[r * a.K + t];
-    for (int t = threadIdx.x; t < nr * a.Nf; t += 256) sd[t] = a.dY[r * a.Nf + t];
+    if constexpr (DYM == DY_F32) {
+      for (int t = threadIdx.x; t < nr * a.Nf; t += 256) sd[t] = a.dY[r * a.Nf + t];
+    } else {
+      const bf16_t* dyh = reinterpret_cast<const bf16_t*>(a.dY) + r * a.Nf;
+      const ActGrad dact(a.act);
+      for (int t = threadIdx.x; t < nr * a.Nf; t += 256) {
+        const float d = __uint_as_float((unsigned)dyh[t] << 16);
+        sd[t] = DYM == DY_BF16_ACT ? __fmul_rn(d, dact(a.pre[r * a.Nf + t])) : d;
+      }
+    }
     __syncthreads();
 #pragma unroll
     for (int o = 0; o < OMAX; ++o) {
@@ -1299,7 +1396,7 @@ static int gemm_launch(const float* A, const void* W, bool w_bf16, float* Y, flo
   if (use_small(K, Nf)) {
     const int Nfp = (Nf + 7) & ~7;
     const int64_t br = rows_per_batch ? rows_per_batch : R;
-    const int64_t max_w = br >= 256 ? 2 : (256 / br + 2);
+    const int64_t max_w = (br >= 256 || !rows_per_batch) ? 2 : (256 / br + 2);  // a shared weight is one weight, however few rows
     size_t smem = (size_t)max_w * K * Nfp * sizeof(float);
     TMGCN_REQUIRE(smem <= 64 * 1024, "gemm: per-slice weights too small a batch (%lld rows)",
                   (long long)br);
@@ -1308,7 +1405,7 @@ static int gemm_launch(const float* A, const void* W, bool w_bf16, float* Y, flo
       smem += (size_t)256 * (Nfp + 1) * sizeof(float);
     }
     const unsigned grid = (unsigned)((R + 255) / 256);
-    hipLaunchKernelGGL(gemm_small_kernel, dim3(grid), dim3(256), smem, st, a);
+    hipLaunchKernelGGL(gemm_small_kernel<float>, dim3(grid), dim3(256), smem, st, a);
     return check_launch("gemm_small");
   }
   const int64_t br = rows_per_batch ? rows_per_batch : R;
@@ -1380,6 +1477,19 @@ extern "C" int64_t tmgcn_gemm_dw_workspace_bytes(int64_t R, int32_t K, int32_t N
   int chunks;
   dw_plan(R, rows_per_batch, &nb, &chunks, &rpc);
   return (nb * chunks + kSyncGroups) * (int64_t)K * Nf * (int64_t)sizeof(float);      // block slabs + the group slabs of slab_tree_finish
+}
+
+// the fixed-order sum of the row-chunk slabs of a dW launch into dW
+static int dw_reduce_launch(const void* workspace, float* dW, int64_t nb, int32_t K, int32_t Nf, int chunks, hipStream_t st) {
+  const int64_t n_out = (int64_t)K * Nf;
+  const int64_t total = nb * n_out;
+  if (total <= 1024 && chunks >= 64)
+    hipLaunchKernelGGL(gemm_dw_reduce_narrow_kernel, dim3((unsigned)total), dim3(256), 0, st, (const float*)workspace,
+                       dW, n_out, chunks);
+  else
+    hipLaunchKernelGGL(gemm_dw_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(DWR_WAVES * 64), 0, st,
+                       (const float*)workspace, dW, n_out, chunks, total);
+  return check_launch("gemm_dw_reduce");
 }
 
 static int gemm_dw_launch(const float* A, const float* dY, const float* pre, int32_t act, float* dW, int64_t R, int32_t K,
@@ -1454,27 +1564,19 @@ static int gemm_dw_launch(const float* A, const float* dY, const float* pre, int
     return check_launch("gemm_dw_narrow");          // reduced by its own last block
   } else if (use_small(K, Nf)) {
     const size_t smem = (size_t)DW_ROWS * (K + Nf) * sizeof(float);
-    hipLaunchKernelGGL(gemm_dw_small_kernel, dim3(gx), dim3(256), smem, st, a);
+    hipLaunchKernelGGL(gemm_dw_small_kernel<DY_F32>, dim3(gx), dim3(256), smem, st, a);
   } else {
     const unsigned gy = (unsigned)(((K + 127) / 128) * ((Nf + 127) / 128));
     const bool x3 = algo == TMGCN_DW_AUTO && K % 4 == 0 && Nf % 4 == 0 &&
                     reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(dY) % 16 == 0;
     if (x3)
-      hipLaunchKernelGGL(gemm_dw_bf16x3_kernel, dim3(gx, gy), dim3(256), 0, st, a);
+      hipLaunchKernelGGL(gemm_dw_bf16x3_kernel<DY_F32>, dim3(gx, gy), dim3(256), 0, st, a);
     else
       hipLaunchKernelGGL(gemm_dw_lds_kernel, dim3(gx, gy), dim3(256), 0, st, a);
   }
   int rc = check_launch("gemm_dw");
   if (rc) return rc;
-  const int64_t n_out = (int64_t)K * Nf;
-  const int64_t total = nb * n_out;
-  if (total <= 1024 && chunks >= 64)
-    hipLaunchKernelGGL(gemm_dw_reduce_narrow_kernel, dim3((unsigned)total), dim3(256), 0, st, (const float*)workspace,
-                       dW, n_out, chunks);
-  else
-    hipLaunchKernelGGL(gemm_dw_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(DWR_WAVES * 64), 0, st,
-                       (const float*)workspace, dW, n_out, chunks, total);
-  return check_launch("gemm_dw_reduce");
+  return dw_reduce_launch(workspace, dW, nb, K, Nf, chunks, st);
 }
 
 extern "C" int tmgcn_gemm_dw_f32(const float* A, const float* dY, float* dW, int64_t R, int32_t K, int32_t Nf,
@@ -1494,4 +1596,105 @@ extern "C" int tmgcn_gemm_dw_act_f32(const float* A, const float* dY, const floa
   TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "gemm_dw_act: unknown activation %d", act);
   TMGCN_REQUIRE(pre_act && reinterpret_cast<uintptr_t>(pre_act) % 8 == 0, "gemm_dw_act: pre_act must be given, 8-byte aligned");
   return gemm_dw_launch(A, dY, pre_act, act, dW, R, K, Nf, rows_per_batch, TMGCN_DW_AUTO, workspace, workspace_bytes, stream);
+}
+
+// ---- the layer-1 GEMM of the bf16 activation path: Y stored in bf16, dW from a bf16 dY ---------------------------
+// The widths both directions have a kernel for: the output width is the K of the bf16 gather that reads Y (a multiple of
+// 8 in [16, 128]); the input width takes the split kernel (a multiple of 4 in [16, 128], one k-chunk) or, below 16, the
+// thread-per-row kernel (Nf <= 64).  dW then runs gemm_dw_bf16x3 / gemm_dw_small — never the narrow kernel (Nf >= 16).
+extern "C" int tmgcn_gemm_bf16y_supported(int32_t K, int32_t Nf) {
+  if (Nf < 16 || Nf > 128 || Nf % 8 != 0) return 0;
+  if (K >= 16) return (K <= 128 && K % 4 == 0) ? 1 : 0;
+  return (K >= 1 && Nf <= 64) ? 1 : 0;
+}
+
+extern "C" int tmgcn_gemm_bf16y(const float* A, const float* W, uint16_t* Y_bf16, float* pre_act, int64_t R, int32_t K,
+                                 int32_t Nf, int64_t rows_per_batch, int64_t w_batch_stride, int32_t act, void* stream) {
+  TMGCN_REQUIRE(R >= 0 && K > 0 && Nf > 0, "gemm_bf16y: bad shape R=%lld K=%d Nf=%d", (long long)R, K, Nf);
+  TMGCN_REQUIRE(rows_per_batch >= 0 && w_batch_stride >= 0, "gemm_bf16y: negative rows_per_batch / w_batch_stride");
+  TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "gemm_bf16y: unknown activation %d", act);
+  TMGCN_REQUIRE(tmgcn_gemm_bf16y_supported(K, Nf),
+                "gemm_bf16y: K=%d, Nf=%d outside the bf16-Y kernels (Nf a multiple of 8 in [16,128]; K a multiple of 4 in "
+                "[16,128], or K < 16 with Nf <= 64): use tmgcn_gemm_f32 and a cast", K, Nf);
+  if (R == 0) return TMGCN_OK;
+  TMGCN_REQUIRE(A && W && Y_bf16, "gemm_bf16y: null pointer");
+  const bool small = use_small(K, Nf);
+  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(A) % (small ? 4 : 16) == 0, "gemm_bf16y: A is not %d-byte aligned", small ? 4 : 16);
+  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(W) % 4 == 0, "gemm_bf16y: W is not 4-byte aligned");
+  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(Y_bf16) % 2 == 0, "gemm_bf16y: Y is not 2-byte aligned");
+  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(pre_act) % 4 == 0, "gemm_bf16y: pre_act is not 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (act == TMGCN_ACT_NONE) pre_act = nullptr;  // as tmgcn_gemm_f32: the pre-activation is stored beside an activation only
+  GemmArgs a{A, W, reinterpret_cast<float*>(Y_bf16), pre_act, R, K, Nf, 0, rows_per_batch, w_batch_stride,
+             act, 0, 0, nullptr, 0, 0, 0, 0, 0};
+  const int64_t br = rows_per_batch ? rows_per_batch : R;
+  if (small) {  // the plan of gemm_launch
+    const int Nfp = (Nf + 7) & ~7;
+    const int64_t max_w = (br >= 256 || !rows_per_batch) ? 2 : (256 / br + 2);
+    size_t smem = (size_t)max_w * K * Nfp * sizeof(float);
+    TMGCN_REQUIRE(smem <= 64 * 1024, "gemm_bf16y: per-slice weights too small a batch (%lld rows)", (long long)br);
+    if (Nfp <= 32 && smem + (size_t)256 * (Nfp + 1) * sizeof(float) <= 64 * 1024) {
+      a.stage_off = (int32_t)(smem / sizeof(float));
+      smem += (size_t)256 * (Nfp + 1) * sizeof(float);
+    }
+    hipLaunchKernelGGL(gemm_small_kernel<bf16_t>, dim3((unsigned)((R + 255) / 256)), dim3(256), smem, st, a);
+    return check_launch("gemm_small (bf16 Y)");
+  }
+  const int64_t nb = (R + br - 1) / br;
+  a.tiles_per_batch = (br + BM - 1) / BM;
+  a.n_tiles = nb * a.tiles_per_batch;
+  TMGCN_REQUIRE(a.n_tiles < (int64_t)0x7fffffff, "gemm_bf16y: shape too large for the tile scheduler");
+  int64_t gx = persistent_grid(gemm_bf16x3_kernel<3, false, bf16_t>, 256);
+  if (gx > a.n_tiles) gx = a.n_tiles;
+  hipLaunchKernelGGL((gemm_bf16x3_kernel<3, false, bf16_t>), dim3((unsigned)gx, 1), dim3(256), 0, st, a);
+  return check_launch("gemm_bf16x3 (bf16 Y)");
+}
+
+extern "C" int tmgcn_gemm_dw_act_bf16(const float* A, const uint16_t* dY_bf16, const float* pre_act, int32_t act, float* dW,
+                                       int64_t R, int32_t K, int32_t Nf, int64_t rows_per_batch, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+  TMGCN_REQUIRE(R >= 0 && K > 0 && Nf > 0, "gemm_dw_act_bf16: bad shape R=%lld K=%d Nf=%d", (long long)R, K, Nf);
+  TMGCN_REQUIRE(rows_per_batch >= 0, "gemm_dw_act_bf16: negative rows_per_batch");
+  TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "gemm_dw_act_bf16: unknown activation %d", act);
+  TMGCN_REQUIRE(tmgcn_gemm_bf16y_supported(K, Nf),
+                "gemm_dw_act_bf16: K=%d, Nf=%d outside the bf16-dY kernels (tmgcn_gemm_bf16y_supported): widen dY and use "
+                "tmgcn_act_bwd_f32 + tmgcn_gemm_dw_f32", K, Nf);
+  if (R == 0) return TMGCN_OK;  // no rows: nothing is launched and dW is left as it is
+  TMGCN_REQUIRE(A && dY_bf16 && dW, "gemm_dw_act_bf16: null pointer");
+  TMGCN_REQUIRE(act == TMGCN_ACT_NONE || pre_act, "gemm_dw_act_bf16: act=%d needs pre_act", act);
+  const bool small = use_small(K, Nf);
+  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(A) % (small ? 4 : 16) == 0, "gemm_dw_act_bf16: A is not %d-byte aligned", small ? 4 : 16);
+  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(dY_bf16) % (small ? 2 : 8) == 0, "gemm_dw_act_bf16: dY is not %d-byte aligned", small ? 2 : 8);
+  TMGCN_REQUIRE(act == TMGCN_ACT_NONE || reinterpret_cast<uintptr_t>(pre_act) % (small ? 4 : 16) == 0,
+                "gemm_dw_act_bf16: pre_act is not %d-byte aligned", small ? 4 : 16);
+  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(dW) % 4 == 0, "gemm_dw_act_bf16: dW is not 4-byte aligned");
+  int64_t nb, rpc;
+  int chunks;
+  dw_plan(R, rows_per_batch, &nb, &chunks, &rpc);
+  const int64_t need = (nb * chunks + kSyncGroups) * (int64_t)K * Nf * (int64_t)sizeof(float);
+  if (!workspace || workspace_bytes < need) {
+    set_error("gemm_dw_act_bf16: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
+    return TMGCN_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  DwArgs a{A, reinterpret_cast<const float*>(dY_bf16), (float*)workspace, R, K, Nf, rows_per_batch ? rows_per_batch : R, chunks, rpc};
+  const bool with_act = act != TMGCN_ACT_NONE;
+  a.pre = with_act ? pre_act : nullptr;
+  a.act = act;
+  const unsigned gx = (unsigned)(nb * chunks);
+  if (small) {
+    const size_t smem = (size_t)DW_ROWS * (K + Nf) * sizeof(float);
+    if (with_act)
+      hipLaunchKernelGGL(gemm_dw_small_kernel<DY_BF16_ACT>, dim3(gx), dim3(256), smem, st, a);
+    else
+      hipLaunchKernelGGL(gemm_dw_small_kernel<DY_BF16>, dim3(gx), dim3(256), smem, st, a);
+  } else {  // K, Nf <= 128: one 128 x 128 output tile
+    if (with_act)
+      hipLaunchKernelGGL(gemm_dw_bf16x3_kernel<DY_BF16_ACT>, dim3(gx, 1), dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL(gemm_dw_bf16x3_kernel<DY_BF16>, dim3(gx, 1), dim3(256), 0, st, a);
+  }
+  int rc = check_launch("gemm_dw_act_bf16");
+  if (rc) return rc;
+  return dw_reduce_launch(workspace, dW, nb, K, Nf, chunks, st);
 }

@@ -2,7 +2,8 @@
 // stored in bf16), which differ only in how a lane's columns are loaded and stored:
 //   * the launch's argument struct MtArgsT<XT, YT> (MtArgs = the fp32 one), row_pos and mop;
 //   * Cols<VEC>, a lane's VEC columns as fp32 registers, and ColIo<E, VEC>, their storage form E in memory
-//     (float: as they are; bf16_t: bf16 bit patterns, widened on load — exact — and rounded to nearest even once on store);
+//     (float: as they are; bf16_t: bf16 bit patterns, widened on load — exact — and rounded to nearest even once on store,
+//     bf16_rne_bits of common.h);
 //   * the sliding-window body (BandBody, band_kernel_body) and the launcher that picks the window width and the row chunks
 //     (launch_band_width).
 // The arithmetic of an output element is the same for every storage form: the same taps in the same order through fmaf on
@@ -13,8 +14,6 @@
 #include "common.h"
 
 namespace tmgcn {
-
-typedef uint16_t bf16_t;  // a bf16 bit pattern: the upper half of an fp32
 
 template <class XT, class YT>
 struct MtArgsT {
@@ -83,13 +82,6 @@ struct Cols<1> {
     v = __uint_as_float(__float_as_uint(v) & bits);
   }
 };
-
-// fp32 -> bf16 bits, round to nearest even: the rounding of st_elem (pointwise.hip), i.e. of the cast launch this replaces
-__device__ __forceinline__ unsigned bf16_rne_bits(float v) {
-  unsigned u = __float_as_uint(v);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
-}
 
 // A lane's VEC columns in memory, stored as E.  float: Cols<VEC>'s own accesses.  bf16_t: VEC = 4 is one 8-byte access
 // (the lanes of a wave cover 512 consecutive bytes), VEC = 1 a 2-byte one; the window and the accumulator stay fp32.

@@ -12,6 +12,8 @@
 //     tmgcn::spmm_gemm_bf16      tmgcn_spmm_gemm_bf16              the same launch on an X stored in bf16
 //     tmgcn::bgemm               tmgcn_gemm_f32                    ehf:222, 330, 344, 349, 486-489
 //     tmgcn::bgemm_dW            tmgcn_gemm_dw_f32                 autograd of ehf:222
+//     tmgcn::gemm_bf16y          tmgcn_gemm_bf16y                  ehf:330-334 with Y stored in bf16 for the layer-2 gather
+//     tmgcn::gemm_dw_act_bf16    tmgcn_gemm_dw_act_bf16            autograd of the same from the gather's bf16 gradient
 //     tmgcn::edge_head_fwd/bwd   tmgcn_edge_head_*_f32             ehf:228-232, 351-355, 491-495
 //     tmgcn::act_fwd/bwd         tmgcn_act_*_f32                   ehf:284-289
 //     tmgcn::wce_fwd/bwd         tmgcn_wce_*_f32                   experiment_reddit_our_link_prediction.py:69, 79
@@ -20,7 +22,7 @@
 //     tmgcn::egcn_fwd/bwd        tmgcn_egcn_fwd / _bwd             evolvegcn_functions.py:80-95 (EvolveGCN-H)
 //     tmgcn::egcn_wide_fwd/bwd   tmgcn_egcn_wide_fwd / _bwd        the same at widths up to 64
 //   differentiable ops (registered under the Autograd key)
-//     tmgcn::m_transform, tmgcn::m_transform_bf16, tmgcn::spmm, tmgcn::feature_gemm, tmgcn::spmm_feature_gemm(_bf16), tmgcn::round_bf16,
+//     tmgcn::m_transform, tmgcn::m_transform_bf16, tmgcn::spmm, tmgcn::feature_gemm(_bf16y), tmgcn::spmm_feature_gemm(_bf16), tmgcn::round_bf16,
 //     tmgcn::edge_head, tmgcn::activation, tmgcn::weighted_ce, tmgcn::wdgcn_lstm, tmgcn::egcn_evolve, tmgcn::egcn_evolve_wide
 //
 // No kernels live here: every launch goes through the C-ABI shared library (libtmgcn_hip.so),
@@ -693,6 +695,53 @@ struct RoundBf16Fn : public torch::autograd::Function<RoundBf16Fn> {
   }
 };
 
+// ---- the layer-1 GEMM of the bf16 activation path (csrc/gemm.hip: tmgcn_gemm_bf16y / tmgcn_gemm_dw_act_bf16) ------------
+bool gemm_bf16y_supported(int64_t K, int64_t Nf) {
+  return K >= 0 && Nf >= 0 && K <= INT32_MAX && Nf <= INT32_MAX && tmgcn_gemm_bf16y_supported((int32_t)K, (int32_t)Nf) != 0;
+}
+static bool aligned_to(const Tensor& t, uintptr_t n) { return !has(t) || reinterpret_cast<uintptr_t>(t.const_data_ptr()) % n == 0; }
+
+// act(A·W) stored in bf16 by the GEMM itself: A [T,N,K] fp32, W fp32 ([K,Nf] shared or [T,K,Nf] per slice); returns the bf16
+// Y and the fp32 pre-activation (want_pre and an activation), bit for bit bgemm's Y through round_bf16, and its pre
+std::tuple<Tensor, Tensor> gemm_bf16y(const Tensor& A, const Tensor& W, int64_t act, bool want_pre) {
+  want(A, "gemm_bf16y A");
+  want(W, "gemm_bf16y W");
+  TORCH_CHECK(A.dim() == 3, "gemm_bf16y: A must be [T,N,K]");
+  c10::DeviceGuard g(A.device());
+  const int64_t T = A.size(0), N = A.size(1), K = A.size(2);
+  const WShape s = w_shape(W, false, T, K, "gemm_bf16y");
+  Tensor Y = at::empty({T, N, s.wn}, A.options().dtype(at::kBFloat16));
+  Tensor pre = (want_pre && act != TMGCN_ACT_NONE) ? at::empty({T, N, s.wn}, A.options()) : Tensor();
+  ok(tmgcn_gemm_bf16y((const float*)ptr(A), (const float*)ptr(W), (uint16_t*)ptr(Y), (float*)ptr(pre), T * N, (int32_t)K,
+                      (int32_t)s.wn, s.per_slice ? N : 0, s.stride, (int32_t)act, stream_of(A)),
+     "tmgcn_gemm_bf16y");
+  return {Y, pre.defined() ? pre : none_like(A)};
+}
+
+// dW = Aᵀ·(widen(dY) ⊙ act'(pre)) in one launch from a bf16 dY (pre: fp32, unused and may be absent for act = none)
+Tensor gemm_dw_act_bf16(const Tensor& A, const Tensor& dY, const OptTensor& pre, int64_t act, bool per_slice) {
+  want(A, "gemm_dw_act_bf16 A");
+  want(dY, "gemm_dw_act_bf16 dY", at::kBFloat16);
+  TORCH_CHECK(A.dim() == 3 && dY.dim() == 3 && A.size(0) == dY.size(0) && A.size(1) == dY.size(1),
+              "gemm_dw_act_bf16: A ", A.sizes(), " and dY ", dY.sizes(), " do not match");
+  const Tensor pr = (act != TMGCN_ACT_NONE && pre.has_value()) ? *pre : Tensor();
+  if (act != TMGCN_ACT_NONE) {
+    want(pr, "gemm_dw_act_bf16 pre-activation");
+    TORCH_CHECK(pr.sizes() == dY.sizes(), "gemm_dw_act_bf16: pre ", pr.sizes(), " and dY ", dY.sizes(), " do not match");
+  }
+  c10::DeviceGuard g(A.device());
+  const int64_t T = A.size(0), N = A.size(1), K = A.size(2), Nf = dY.size(2), R = T * N;
+  const int64_t rpb = per_slice ? N : 0;
+  if (R == 0) return per_slice ? at::zeros({T, K, Nf}, A.options()) : at::zeros({K, Nf}, A.options());
+  const int64_t need = tmgcn_gemm_dw_workspace_bytes(R, (int32_t)K, (int32_t)Nf, rpb);
+  Tensor ws = at::empty({need > 0 ? need : 1}, A.options().dtype(at::kByte));
+  Tensor dW = per_slice ? at::empty({T, K, Nf}, A.options()) : at::empty({K, Nf}, A.options());
+  ok(tmgcn_gemm_dw_act_bf16((const float*)ptr(A), (const uint16_t*)ptr(dY), (const float*)ptr(pr), (int32_t)act, (float*)ptr(dW), R,
+                            (int32_t)K, (int32_t)Nf, rpb, ptr(ws), ws.numel(), stream_of(A)),
+     "tmgcn_gemm_dw_act_bf16");
+  return dW;
+}
+
 bool layer12_supported(int64_t K0, int64_t F, int64_t Nf) { return tmgcn_layer12_supported((int32_t)K0, (int32_t)F, (int32_t)Nf) != 0; }
 // ---- WD-GCN (wd_gcn_functions.py:66-98): relu(AX·W) + the LSTM recurrence, and its BPTT ----------------------------
 // `wide` selects the kernels of csrc/wdgcn_wide.hip (widths up to 64) through tmgcn_wdgcn_wide_*: the same operator,
@@ -1086,6 +1135,53 @@ struct FeatureGemmFn : public torch::autograd::Function<FeatureGemmFn> {
       dW = bgemm_dW(A, dY, W.dim() == 3, TMGCN_DW_AUTO);  // summed in fp32, rounded once for a bf16 parameter
       if (dW.scalar_type() != W.scalar_type()) dW = dW.to(W.scalar_type());
     }
+    return {dA, dW, Tensor()};
+  }
+};
+
+// act(A·W) with the result STORED in bf16 — layer 1 in front of the bf16 gather (EmbeddingGCN2(act_dtype=bfloat16), default
+// branch).  One launch each way where the kernels of tmgcn_gemm_bf16y cover the widths and the operands are aligned; else
+// the composition they replace (bgemm + cast forward; widen + act_bwd + bgemm / bgemm_dW backward), which gives the same bits.
+struct FeatureGemmBf16yFn : public torch::autograd::Function<FeatureGemmBf16yFn> {
+  static bool small_route(int64_t K) { return K < 16; }
+  static Tensor forward(AutogradContext* ctx, const Tensor& A, const Tensor& W, int64_t act) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    const bool fused = A.defined() && A.dim() == 3 && W.defined() && W.scalar_type() == at::kFloat && A.numel() > 0 &&
+                       gemm_bf16y_supported(A.size(-1), W.size(-1)) && aligned_to(A, small_route(A.size(-1)) ? 4 : 16);
+    Tensor Y, pre;
+    if (fused) {
+      std::tie(Y, pre) = gemm_bf16y(A, W, act, act != TMGCN_ACT_NONE);
+    } else {
+      Tensor Yf;
+      std::tie(Yf, pre) = bgemm(A, W, false, act, act != TMGCN_ACT_NONE, TMGCN_GEMM_AUTO);
+      Y = Yf.numel() ? cast_multi({Yf}, true)[0] : Yf.to(at::kBFloat16);
+    }
+    ctx->saved_data["act"] = act;
+    ctx->save_for_backward({A, W, pre});
+    return Y;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    auto sv = ctx->get_saved_variables();
+    const Tensor &A = sv[0], &W = sv[1], &pre = sv[2];
+    const int64_t act = ctx->saved_data["act"].toInt();
+    Tensor dY = grads[0].contiguous();
+    Tensor dA, dW;
+    const bool small = small_route(A.size(-1));
+    // the gather's bf16 gradient as it arrives, act' folded into the dW operand load: no widened dY, no dY ⊙ act'(pre)
+    const bool fused = dY.scalar_type() == at::kBFloat16 && !ctx->needs_input_grad(0) && ctx->needs_input_grad(1) && A.dim() == 3 &&
+                       dY.numel() > 0 && gemm_bf16y_supported(A.size(-1), dY.size(-1)) && aligned_to(A, small ? 4 : 16) &&
+                       aligned_to(dY, small ? 2 : 8) && (act == TMGCN_ACT_NONE || aligned_to(pre, small ? 4 : 16));
+    if (fused) {
+      dW = gemm_dw_act_bf16(A, dY, pre, act, W.dim() == 3);
+    } else {
+      if (dY.scalar_type() == at::kBFloat16) dY = dY.numel() ? cast_multi({dY}, false)[0] : dY.to(at::kFloat);
+      if (act != TMGCN_ACT_NONE) dY = act_bwd(pre, dY, act);
+      if (ctx->needs_input_grad(0)) dA = std::get<0>(bgemm(dY, W, true, TMGCN_ACT_NONE, false, TMGCN_GEMM_AUTO));
+      if (ctx->needs_input_grad(1)) dW = bgemm_dW(A, dY, W.dim() == 3, TMGCN_DW_AUTO);
+    }
+    // summed in fp32, rounded once for a bf16 parameter
+    if (dW.defined() && dW.scalar_type() != W.scalar_type()) dW = dW.to(W.scalar_type());
     return {dA, dW, Tensor()};
   }
 };
@@ -1516,6 +1612,7 @@ Tensor spmm_ad(const Tensor& X, const Tensor& rowptr, const Tensor& col, const T
                        at::GradMode::is_enabled() && X.requires_grad());
 }
 Tensor feature_gemm_ad(const Tensor& A, const Tensor& W, int64_t act) { return FeatureGemmFn::apply(A, W, act); }
+Tensor feature_gemm_bf16y_ad(const Tensor& A, const Tensor& W, int64_t act) { return FeatureGemmBf16yFn::apply(A, W, act); }
 Tensor spmm_feature_gemm_ad(const Tensor& X, const Tensor& W, const Tensor& rowptr, const Tensor& col,
                             const Tensor& val, const OptTensor& t_rowptr, const OptTensor& t_col,
                             const OptTensor& t_val, int64_t N, double avg, int64_t act, int64_t grid_reserve,
@@ -1627,6 +1724,9 @@ TORCH_LIBRARY(tmgcn, m) {
   m.def("bgemm(Tensor A, Tensor W, bool trans_w, int act, bool want_pre, int algo) -> (Tensor, Tensor)");
   m.def("bgemm_dW(Tensor A, Tensor dY, bool per_slice, int algo) -> Tensor");
   m.def("bgemm_dW_act(Tensor A, Tensor dY, Tensor pre, int act, bool per_slice) -> Tensor");
+  m.def("gemm_bf16y(Tensor A, Tensor W, int act, bool want_pre) -> (Tensor, Tensor)");
+  m.def("gemm_dw_act_bf16(Tensor A, Tensor dY, Tensor? pre, int act, bool per_slice) -> Tensor");
+  m.def("gemm_bf16y_supported(int K, int Nf) -> bool", &gemm_bf16y_supported);
   m.def("edge_head_fwd(Tensor Z2, Tensor src, Tensor dst, Tensor U) -> Tensor");
   m.def("edge_head_bwd(Tensor Z2, Tensor src, Tensor dst, Tensor U, Tensor dout, Tensor eptr, Tensor eidx, "
         "bool need_dz, bool need_du) -> (Tensor, Tensor)");
@@ -1653,6 +1753,7 @@ TORCH_LIBRARY(tmgcn, m) {
         "int N, float avg_nnz_per_row, Tensor? giant_rows=None, Tensor? giant_chunks=None, Tensor? t_giant_rows=None, "
         "Tensor? t_giant_chunks=None) -> Tensor");
   m.def("feature_gemm(Tensor A, Tensor W, int act) -> Tensor");
+  m.def("feature_gemm_bf16y(Tensor A, Tensor W, int act) -> Tensor");
   m.def("spmm_feature_gemm(Tensor X, Tensor W, Tensor rowptr, Tensor col, Tensor val, Tensor? t_rowptr, "
         "Tensor? t_col, Tensor? t_val, int N, float avg_nnz_per_row, int act, int grid_reserve, Tensor? giant_rows=None, "
         "Tensor? giant_chunks=None, Tensor? t_giant_rows=None, Tensor? t_giant_chunks=None) -> Tensor");
@@ -1703,6 +1804,7 @@ static void impl_differentiable(torch::Library& m) {
   m.impl("m_transform_bf16", &m_transform_bf16_ad);
   m.impl("spmm", &spmm_ad);
   m.impl("feature_gemm", &feature_gemm_ad);
+  m.impl("feature_gemm_bf16y", &feature_gemm_bf16y_ad);
   m.impl("spmm_feature_gemm", &spmm_feature_gemm_ad);
   m.impl("spmm_feature_gemm_bf16", &spmm_feature_gemm_bf16_ad);
   m.impl("round_bf16", &round_bf16_ad);
@@ -1730,6 +1832,8 @@ TORCH_LIBRARY_IMPL(tmgcn, CUDA, m) {
   m.impl("bgemm", &bgemm);
   m.impl("bgemm_dW", &bgemm_dW);
   m.impl("bgemm_dW_act", &bgemm_dW_act);
+  m.impl("gemm_bf16y", &gemm_bf16y);
+  m.impl("gemm_dw_act_bf16", &gemm_dw_act_bf16);
   m.impl("edge_head_fwd", &edge_head_fwd);
   m.impl("edge_head_bwd", &edge_head_bwd);
   m.impl("act_fwd", &act_fwd);

@@ -452,10 +452,12 @@ class EmbeddingGCN2(_Head, _Deliver, _Sharding, nn.Module):
         if self.use_Minv:
             Y = ops.activation(self._mt(ops.feature_gemm(AtXt, W1), self.Minv), self.nonlin2)
         else:
-            Y = ops.feature_gemm(AtXt, W1, act=self.nonlin2)
+            # act_dtype in the default branch: no M product in front of layer 2, so the GEMM stores the gathered operand
+            # in bf16 itself (ops.feature_gemm, out_dtype) and its dW reads the gather's bf16 gradient — no cast launch
+            bf16_y = self.act_dtype is not None and not self.apply_M_twice
+            Y = ops.feature_gemm(AtXt, W1, act=self.nonlin2, out_dtype=self.act_dtype if bf16_y else None)
         # second layer — always the training adjacency self.At (ehf:339, 343, 348); sharded, the
         # M / M⁻¹ products below are the only steps that exchange activations between ranks
-        store = ops.round_bf16 if self.act_dtype is not None else (lambda x: x)    # the gathered operand, stored in act_dtype
         # act_dtype: the M product writes the bf16 operand itself and its backward reads the gather's bf16 gradient (one
         # launch each way, ops.m_transform; act_dtype refuses group=, so this is never the sharded exchange)
         mt_store = (lambda y: ops.m_transform(y, self.Mop, out_dtype=self.act_dtype)) if self.act_dtype is not None \
@@ -467,7 +469,7 @@ class EmbeddingGCN2(_Head, _Deliver, _Sharding, nn.Module):
             if self.apply_M_three_times:
                 Z = self._mt(Z, self.Mop)                                          # ehf:346
         else:
-            Z = ops.spmm_feature_gemm(self.At, store(Y), W2)                       # ehf:348-349
+            Z = ops.spmm_feature_gemm(self.At, Y, W2)                              # ehf:348-349
         return Z, eidx, U, None
 
 

@@ -359,18 +359,38 @@ class HipKernels:
         return Y, (AX if AX.numel() else None), (pre if pre.numel() else None)
 
     # P3 ---------------------------------------------------------------------------------
-    def gemm(self, A: torch.Tensor, W: torch.Tensor, trans_w=False, act=None, want_pre=False, algo=None):
+    def gemm_bf16y_supported(self, K: int, Nf: int) -> bool:
+        return bool(_lib.load().tmgcn_gemm_bf16y_supported(K, Nf))
+
+    def gemm(self, A: torch.Tensor, W: torch.Tensor, trans_w=False, act=None, want_pre=False, algo=None, out_dtype=None):
         """A [T,N,K] · W ([K,Nf] shared or [T,K,Nf] per slice; transposed if trans_w).  W may be stored
         in bf16 (tmgcn_gemm_bf16w_f32: half the matrix-core work, same bits as its fp32-widened copy).
         algo: None / "auto" (bf16x3 split on the bf16 matrix cores for K a multiple of 4 in [16,128])
-        or "f32mfma" (exact-f32 MFMA: bitwise an fmaf chain) — per call."""
+        or "f32mfma" (exact-f32 MFMA: bitwise an fmaf chain) — per call.
+        out_dtype=torch.bfloat16: Y stored in bf16 by the GEMM itself (tmgcn_gemm_bf16y; timer tag gemm_bf16y) — an fp32 W,
+        trans_w=False, the default algo and the widths of gemm_bf16y_supported only; the pre-activation stays fp32."""
+        if _y_bf16(out_dtype):
+            if trans_w or algo not in (None, "auto"):
+                raise RuntimeError("out_dtype=torch.bfloat16 is the forward product with the default algorithm only")
+            Y, pre = self._run("gemm_bf16y", A.device, lambda: self.ops.gemm_bf16y(A, W, _lib.ACT_IDS[act], bool(want_pre)))
+            return (Y, pre if pre.numel() else None) if want_pre else Y
         Y, pre = self._run("gemm_dA" if trans_w else "gemm", A.device, lambda: self.ops.bgemm(
             A, W, bool(trans_w), _lib.ACT_IDS[act], bool(want_pre), _lib.GEMM_ALGOS[algo]))
         return (Y, pre if pre.numel() else None) if want_pre else Y
 
-    def gemm_dw(self, A: torch.Tensor, dY: torch.Tensor, per_slice: bool, algo=None) -> torch.Tensor:
+    def gemm_dw(self, A: torch.Tensor, dY: torch.Tensor, per_slice: bool, algo=None, pre=None, act=None) -> torch.Tensor:
         """dW = Σ_r A[r]ᵀ dY[r].  algo: None / "auto" (bf16x3 split on the bf16 matrix cores where the
-        shapes allow) or "f32mfma" (exact-f32 MFMA kernel) — per call."""
+        shapes allow) or "f32mfma" (exact-f32 MFMA kernel) — per call.
+        A dY stored in bf16 is widened as the kernel loads it and, with pre= and act=, multiplied by act'(pre) there:
+        dW = Σ_r A[r]ᵀ (dY[r] ⊙ act'(pre[r])) in one launch (tmgcn_gemm_dw_act_bf16; timer tag gemm_dw_act_bf16), on the widths
+        of gemm_bf16y_supported, default algo."""
+        if dY.dtype == torch.bfloat16:
+            if algo not in (None, "auto"):
+                raise RuntimeError("a bf16 dY takes the default algorithm only")
+            return self._run("gemm_dw_act_bf16", A.device, lambda: self.ops.gemm_dw_act_bf16(
+                A, dY, pre, _lib.ACT_IDS[act], bool(per_slice)))
+        if pre is not None or _lib.ACT_IDS[act]:
+            raise RuntimeError("pre= / act= fold the activation gradient into the dW of a bf16 dY; an fp32 dY takes act_bwd first")
         return self._run("gemm_dW", A.device, lambda: self.ops.bgemm_dW(A, dY, bool(per_slice), _lib.DW_ALGOS[algo]))
 
     # P4 ---------------------------------------------------------------------------------
@@ -465,6 +485,40 @@ class _FeatureGemm(torch.autograd.Function):
         dW = kernels.gemm_dw(A, dY, per_slice=W.dim() == 3) if ctx.needs_input_grad[1] else None
         if dW is not None and dW.dtype != W.dtype:
             dW = dW.to(W.dtype)              # a bf16-stored parameter: summed in fp32, rounded once
+        return dA, dW, None
+
+
+class _FeatureGemmBf16y(torch.autograd.Function):
+    """_FeatureGemm with Y stored in bf16 by the GEMM (the widths of gemm_bf16y_fused, an fp32 W): one launch each way when
+    the gradient arrives in bf16 and only W needs one; else the composition."""
+
+    @staticmethod
+    def forward(ctx, A, W, act):
+        ctx.act = act if _lib.ACT_IDS[act] else None
+        if ctx.act is not None:
+            Y, pre = kernels.gemm(A, W, act=act, want_pre=True, out_dtype=torch.bfloat16)
+            ctx.save_for_backward(A, W, pre)
+        else:
+            Y = kernels.gemm(A, W, out_dtype=torch.bfloat16)
+            ctx.save_for_backward(A, W)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        dY = dY.contiguous()
+        A, W, *rest = ctx.saved_tensors
+        pre = rest[0] if rest else None
+        small = A.shape[-1] < 16
+        if (dY.dtype == torch.bfloat16 and not ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
+                and A.data_ptr() % (4 if small else 16) == 0 and dY.data_ptr() % (2 if small else 8) == 0
+                and (pre is None or pre.data_ptr() % (4 if small else 16) == 0)):
+            return None, kernels.gemm_dw(A, dY, per_slice=W.dim() == 3, pre=pre, act=ctx.act), None
+        if dY.dtype == torch.bfloat16:
+            dY = kernels.ops.widen_params([dY])[0]
+        if ctx.act is not None:
+            dY = kernels.act_bwd(pre, dY, ctx.act)
+        dA = kernels.gemm(dY, W, trans_w=True) if ctx.needs_input_grad[0] else None
+        dW = kernels.gemm_dw(A, dY, per_slice=W.dim() == 3) if ctx.needs_input_grad[1] else None
         return dA, dW, None
 
 
@@ -595,17 +649,43 @@ def spmm(A: BatchedCSR, X: torch.Tensor) -> torch.Tensor:
     return _Spmm.apply(X, A)
 
 
-def feature_gemm(A: torch.Tensor, W: torch.Tensor, act=None) -> torch.Tensor:
-    """P3 (+ fused P5): act(A · W), W shared ([K,Nf]) or per slice ([T,K,Nf])."""
-    if _registered():
-        return kernels.ops.feature_gemm(A, W, _lib.ACT_IDS[act])
-    return _FeatureGemm.apply(A, W, act)
-
-
 def _y_bf16(out_dtype) -> bool:
     if out_dtype not in (None, torch.float32, torch.bfloat16):
         raise RuntimeError(f"out_dtype must be None, torch.float32 or torch.bfloat16, got {out_dtype}")
     return out_dtype == torch.bfloat16
+
+
+# Each direction of the fused bf16-Y GEMM is kept only where it was measured faster than the launches it replaces
+# (tools/bf16_gemm_ab.py, profiles/bf16_gemm_ab.json); a direction that is off keeps the composition, with the same bits.
+_GEMM_BF16Y_KEEP = {"forward": True, "backward": True}
+
+
+def gemm_bf16y_fused(K: int, Nf: int) -> bool:
+    """True when feature_gemm(..., out_dtype=torch.bfloat16) at these widths is ONE launch each way (csrc/gemm.hip: the GEMM
+    stores bf16 itself, its dW reads the bf16 gradient and applies act'): Nf a multiple of 8 in [16,128] with K a multiple
+    of 4 in [16,128], or K < 16 with Nf <= 64.  False: the fp32 GEMM and the cast launches."""
+    return (kernels.name == "hip" and _GEMM_BF16Y_KEEP["forward"] and _GEMM_BF16Y_KEEP["backward"]
+            and kernels.gemm_bf16y_supported(int(K), int(Nf)))
+
+
+def feature_gemm(A: torch.Tensor, W: torch.Tensor, act=None, out_dtype=None) -> torch.Tensor:
+    """P3 (+ fused P5): act(A · W), W shared ([K,Nf]) or per slice ([T,K,Nf]).
+
+    out_dtype=torch.bfloat16 returns the activation stored in bf16 — the fp32 result rounded to nearest even once, as the
+    bf16 gather of the next layer reads it; its gradient may arrive in bf16 or fp32.  Where gemm_bf16y_fused(K, Nf) holds
+    (and W is fp32) that is one launch each way: the GEMM stores bf16 itself, and when only W needs a gradient its dW reads
+    the bf16 gradient and applies act'(pre) as it loads.  Elsewhere it is round_bf16(feature_gemm(A, W, act)): the same
+    bits."""
+    if not _y_bf16(out_dtype):
+        if _registered():
+            return kernels.ops.feature_gemm(A, W, _lib.ACT_IDS[act])
+        return _FeatureGemm.apply(A, W, act)
+    if W.dtype == torch.float32 and gemm_bf16y_fused(A.shape[-1], W.shape[-1]):
+        if _registered():
+            return kernels.ops.feature_gemm_bf16y(A, W, _lib.ACT_IDS[act])
+        if A.data_ptr() % (4 if A.shape[-1] < 16 else 16) == 0:
+            return _FeatureGemmBf16y.apply(A, W, act)
+    return round_bf16(feature_gemm(A, W, act=act))
 
 
 def spmm_gemm_bf16_supported(K: int, Nf: int) -> bool:

@@ -20,6 +20,7 @@ to enforce this, so it is checked on what the build produced:
                    (`make print-hipcc`), run the --asm check, then --lib on the in-tree library.
   --selftest       negative tests of the checker itself (violations must be reported).
 
+The bf16-Y instantiation of gemm_bf16x3 is scanned and counted with the others and reported only on a violation.
 Every kernel is scanned from its label to .Lfunc_end (not to the first s_endpgm: early-exit blocks
 are followed by more code).  Kernels not listed below whose inline asm names v192+ fail the check
 too (a new user of async_stage.h must be listed).  Exit status 0 = clean, 1 = violation.
@@ -37,9 +38,13 @@ CSRC = os.path.join(ROOT, "tm-gcn_amd", "csrc")
 LLVM = os.environ.get("TMGCN_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 ZONE = 192                      # lowest register async_stage.h ever names
 KERNELS = {                     # source file -> {mangled-name fragment: (first reserved VGPR, expected instantiations)}
-    "gemm.hip": {"gemm_bf16x3_kernel": (192, 4)},
+    "gemm.hip": {"gemm_bf16x3_kernel": (192, 5)},
     "mtransform.hip": {"mtransform_bf16x3_kernel": (192, 1)},
 }
+# Instantiations that differ from a listed kernel only in how the output is STORED (gemm_bf16x3_kernel<WP, CH, bf16_t>: the
+# same body, a bf16 epilogue) are scanned and counted like every other one, and reported only when they violate: the report
+# stays one line per fp32 kernel.
+STORAGE_VARIANT = re.compile(r"gemm_bf16x3_kernelILi\d+ELb[01]EtEE")
 # Calls: s_swappc_b64 / s_call_b64, and in compiler assembly any pc-relative reference to a SYMBOL
 # (@rel32@ / @gotpcrel32@: the address of a function is being formed, e.g. for a tail call).
 # s_setpc_b64 alone is NOT a call: large kernels use s_getpc/s_add/s_setpc for long branches to
@@ -106,7 +111,7 @@ def check_asm(paths, kernels, quiet=False):
             seen[frag] = seen.get(frag, 0) + 1
             if not asm_zone:
                 hits.append("no inline-asm use of the reserved zone found (is this still an async_stage.h kernel?)")
-            if not quiet or hits:
+            if (not quiet and not STORAGE_VARIANT.search(name)) or hits:
                 print(f"{name}: compiler code uses v0..v{top}, reserved zone starts at v{first}: "
                       f"{'OK' if not hits else f'{len(hits)} VIOLATIONS, e.g. ' + hits[0]}")
             bad += bool(hits)
@@ -190,7 +195,7 @@ def check_lib(lib, kernels, quiet=False, allow_missing=False):
                 if not zone_used:
                     hits.append("the reserved zone is never used (is this still an async_stage.h kernel?)")
                 seen[frag] = seen.get(frag, 0) + 1
-                if not quiet or hits:
+                if (not quiet and not STORAGE_VARIANT.search(cur)) or hits:
                     print(f"{os.path.basename(lib)}:{cur}: only async_stage.h's own instruction shapes touch v{first}..: "
                           f"{'OK' if not hits else f'{len(hits)} VIOLATIONS, e.g. ' + hits[0]}")
                 bad += bool(hits)
