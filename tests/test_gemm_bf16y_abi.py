@@ -103,6 +103,71 @@ def test_empty_extent_is_ok_without_a_launch(over):
     assert _dw(**over) == OK
 
 
+def _fwd_f32(**over):
+    """tmgcn_gemm_f32, likewise."""
+    a = dict(A=0x10000, W=0x20000, Y=0x30000, pre=0x40000, R=100, K=32, Nf=24, trans_w=0, rows_per_batch=0, w_batch_stride=0, act=3,
+             algo=0, stream=None)
+    a.update(over)
+    order = ("A", "W", "Y", "pre", "R", "K", "Nf", "trans_w", "rows_per_batch", "w_batch_stride", "act", "algo", "stream")
+    return _lib.load().tmgcn_gemm_f32(*(a[k] for k in order))
+
+
+def _dw_f32(fold, **over):
+    """tmgcn_gemm_dw_f32, or with fold tmgcn_gemm_dw_act_f32 (the narrow kernel's fold of act'), likewise."""
+    a = dict(A=0x10000, dY=0x30000, pre=0x40000, act=3, dW=0x50000, R=100, K=32, Nf=24, rows_per_batch=0, algo=0, ws=0x60000,
+             ws_bytes=None, stream=None)
+    a.update(over)
+    if a["ws_bytes"] is None:
+        a["ws_bytes"] = _lib.load().tmgcn_gemm_dw_workspace_bytes(a["R"], a["K"], a["Nf"], a["rows_per_batch"])
+    if fold:
+        order = ("A", "dY", "pre", "act", "dW", "R", "K", "Nf", "rows_per_batch", "ws", "ws_bytes", "stream")
+        return _lib.load().tmgcn_gemm_dw_act_f32(*(a[k] for k in order))
+    order = ("A", "dY", "dW", "R", "K", "Nf", "rows_per_batch", "algo", "ws", "ws_bytes", "stream")
+    return _lib.load().tmgcn_gemm_dw_f32(*(a[k] for k in order))
+
+
+def test_fp32_entries_keep_their_own_rule_for_an_empty_extent():
+    """The launchers are shared with the bf16 entries; the fp32 ones keep their own R = 0 rule.  The forward launches nothing
+    and returns OK before it looks at an operand.  dW zero-fills what it is given — a launch, so its OK return is held on the
+    GPU (test_gpu_gemm_bf16y.py) — and here refuses only a dW that is not there, where the bf16 entry returns OK."""
+    assert _fwd_f32(R=0) == OK
+    assert _fwd_f32(R=0, A=None, W=None, Y=None, pre=None) == OK
+    assert _fwd_f32(R=0, K=256) == OK and _fwd_f32(R=0, K=132, trans_w=1, algo=1) == OK       # no bf16-Y domain here
+    for fold in (False, True):
+        k = dict(K=4, Nf=8) if fold else {}
+        assert _dw_f32(fold, R=0, A=None, dY=None, ws=None, ws_bytes=0, dW=None, **k) == INVALID
+        assert b"dW" in _lib.load().tmgcn_last_error()
+    assert _dw(R=0, A=None, dY=None, ws=None, ws_bytes=0, dW=None) == OK
+
+
+@pytest.mark.parametrize("K", [132, 256])
+def test_forward_never_reaches_a_k_chunked_launch(K):
+    """128 < K <= 512 is the k-chunked form of the fp32 entry, whose chunks add to an fp32 Y: the bf16-Y entry names the
+    width and refuses, aligned operands or not."""
+    lib = _lib.load()
+    assert _fwd(K=K) == INVALID
+    msg = lib.tmgcn_last_error()
+    assert len(msg) > 0 and f"K={K}".encode() in msg
+    assert _fwd(K=K, R=0) == INVALID
+
+
+@pytest.mark.parametrize("K", [2, 32], ids=["small_route", "split_route"])
+def test_every_dw_entry_asks_for_the_same_workspace(K):
+    """One byte short of tmgcn_gemm_dw_workspace_bytes is the workspace status for the bf16 entry on both of its routes
+    and for the two fp32 entries, with that same value."""
+    lib = _lib.load()
+    need = lib.tmgcn_gemm_dw_workspace_bytes(100, K, 24, 0)
+    assert need > 0
+    for call in (lambda **o: _dw(K=K, **o), lambda **o: _dw_f32(False, K=K, **o)):
+        assert call(ws_bytes=need - 1) == WORKSPACE
+        assert b"workspace" in lib.tmgcn_last_error()
+        assert call(ws=None) == WORKSPACE
+    # the fold of tmgcn_gemm_dw_act_f32 exists for even K, Nf <= 8 only
+    need8 = lib.tmgcn_gemm_dw_workspace_bytes(100, K if K <= 8 else 8, 8, 0)
+    assert _dw_f32(True, K=K if K <= 8 else 8, Nf=8, ws_bytes=need8 - 1) == WORKSPACE
+    assert b"workspace" in lib.tmgcn_last_error()
+
+
 def test_out_dtype_rule_of_the_python_operator():
     A, W = torch.zeros(2, 8, 16), torch.zeros(16, 16)
     for bad in (torch.float16, torch.float64, torch.int32):

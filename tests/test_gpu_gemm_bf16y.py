@@ -228,6 +228,35 @@ def test_dw_per_slice_weights(K, Nf, T, N):
     assert_close(dW, ref, REL_TOL, f"per-slice dW K={K} Nf={Nf}")
 
 
+@pytest.mark.parametrize("K,Nf", [(32, 24), (2, 16), (4, 8)], ids=["split", "small", "narrow"])
+def test_dw_of_no_rows_is_each_entry_points_own_rule(K, Nf):
+    """R = 0 through the one dW launcher: tmgcn_gemm_dw_f32 and tmgcn_gemm_dw_act_f32 zero-fill the dW they are given and
+    return OK; tmgcn_gemm_dw_act_bf16 returns OK and leaves dW as it is (the operator allocates zeros instead)."""
+    lib = _lib.load()
+    dW = torch.full((K, Nf), 7.0, device=DEV)
+    ws = torch.empty(64, dtype=torch.uint8, device=DEV)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if lib.tmgcn_gemm_bf16y_supported(K, Nf):
+        assert lib.tmgcn_gemm_dw_act_bf16(None, None, None, 0, dW.data_ptr(), 0, K, Nf, 0, ws.data_ptr(), ws.numel(), st) == 0
+        torch.cuda.synchronize()
+        assert bool((dW == 7.0).all())
+    if lib.tmgcn_gemm_dw_act_supported(K, Nf):
+        assert lib.tmgcn_gemm_dw_act_f32(None, None, ws.data_ptr(), 3, dW.data_ptr(), 0, K, Nf, 0, None, 0, st) == 0
+        torch.cuda.synchronize()
+        assert bool((dW == 0).all())
+        dW.fill_(7.0)
+    assert lib.tmgcn_gemm_dw_f32(None, None, dW.data_ptr(), 0, K, Nf, 0, 0, None, 0, st) == 0
+    torch.cuda.synchronize()
+    assert bool((dW == 0).all())
+    A, dY = torch.empty(2, 0, K, device=DEV), torch.empty(2, 0, Nf, device=DEV)
+    got = ops.kernels.gemm_dw(A, dY, False)
+    assert got.shape == (K, Nf) and not bool(got.any())
+    for per_slice, shape in ((False, (K, Nf)), (True, (2, K, Nf))):
+        if lib.tmgcn_gemm_bf16y_supported(K, Nf):
+            got = ops.kernels.gemm_dw(A, dY.to(BF16), per_slice)
+            assert got.shape == shape and got.dtype == F32 and not bool(got.any())
+
+
 def test_dw_long_chunks_run_the_ring_and_the_flush():
     """Enough rows per chunk for the steady-state loop (unconditional loads, a flush every four steps) and its drain."""
     R, K, Nf = 40_000, 128, 128

@@ -364,3 +364,38 @@ def test_registered_cpp_autograd_and_python_autograd_paths_are_bit_identical():
     for n in g_c:
         assert torch.equal(g_c[n], g_p[n]), n
     assert_close(out_c, d["logits"], TOL, "logits")
+
+
+@pytest.mark.parametrize("F0", [16, 2], ids=["K16_split", "K2_thread_per_row"])
+@pytest.mark.parametrize("branch, want_tags", [(dict(), {"gemm_bf16y", "gemm_dw_act_bf16"}),
+                                               (dict(apply_M_twice=True), {"mtransform_bf16", "mtransform_bf16_T"})],
+                         ids=["default", "M_twice"])
+def test_registered_and_python_autograd_paths_are_bit_identical_with_bf16_activations(branch, want_tags, F0):
+    """The same identity for EmbeddingGCN2(act_dtype=bf16), whose layer-1 GEMM (default branch) and M-transform
+    (apply_M_twice) store bf16 and read a bf16 gradient: the registered C++ autograd and the Python autograd under a
+    KernelTimer are two statements of one function each, and must give logits, loss and every gradient bit for bit.
+    N = 70 is no multiple of the 64-row tile; an input width of 2 takes the thread-per-row GEMM (K < 16)."""
+    from tmgcn_amd import ops, synth
+    g = synth.dynamic_graph(T=3, N=70, edges_per_slice=40, seed=2, no_diag=2, F0=F0)
+    At, X, M = g.At_list(), torch.from_numpy(g.X).float(), torch.from_numpy(g.M)
+    edges, labels = torch.from_numpy(g.edges), torch.from_numpy(g.labels)
+
+    def run(timed):
+        torch.manual_seed(0)
+        m = ehf.EmbeddingGCN2(At, X, edges, M, hidden_feat=[16, 16, 2], condensed_W=True, use_Minv=False, nonlin2="selu",
+                              act_dtype=torch.bfloat16, **branch)
+        ops.kernels.timer = ops.KernelTimer() if timed else None
+        try:
+            out, loss, grads = _loss_grads(m, labels)
+            tags = set(ops.kernels.timer.summary()) if timed else set()
+        finally:
+            ops.kernels.timer = None
+        return out, loss, grads, tags
+
+    out_c, loss_c, g_c, _ = run(False)
+    out_p, loss_p, g_p, tags = run(True)
+    assert want_tags <= tags, tags
+    assert torch.equal(out_c, out_p) and loss_c == loss_p
+    assert set(g_c) == set(g_p) and all(v is not None for v in g_c.values())
+    for n in g_c:
+        assert torch.equal(g_c[n], g_p[n]), n

@@ -1381,76 +1381,78 @@ static void dw_plan(int64_t R, int64_t rows_per_batch, int64_t* n_batch, int* ch
 
 using namespace tmgcn;
 
-static int gemm_launch(const float* A, const void* W, bool w_bf16, float* Y, float* pre_act, int64_t R,
-                       int32_t K, int32_t Nf, int32_t trans_w, int64_t rows_per_batch,
-                       int64_t w_batch_stride, int32_t act, int32_t algo, void* stream) {
-  TMGCN_REQUIRE(R >= 0 && K > 0 && Nf > 0, "gemm: bad shape R=%lld K=%d Nf=%d", (long long)R, K, Nf);
-  TMGCN_REQUIRE(algo == TMGCN_GEMM_AUTO || algo == TMGCN_GEMM_F32MFMA, "gemm: unknown algo %d", algo);
-  TMGCN_REQUIRE(rows_per_batch >= 0, "gemm: negative rows_per_batch");
-  TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "gemm: unknown activation %d", act);
+// The one forward launcher.  y_bf16: Y is stored in bf16 (tmgcn_gemm_bf16y).  Only gemm_small<bf16_t> and the one-chunk
+// gemm_bf16x3<3, false, bf16_t> can store that, so a bf16 Y REFUSES what would take another kernel — the widths outside
+// tmgcn_gemm_bf16y_supported, a transposed or bf16 W, the exact-f32 algorithm, a misaligned A — where an fp32 Y falls back
+// to the k-chunked form or to gemm_mfma.
+static int gemm_launch(const char* who, const float* A, const void* W, bool w_bf16, void* Y, bool y_bf16, float* pre_act,
+                       int64_t R, int32_t K, int32_t Nf, int32_t trans_w, int64_t rows_per_batch, int64_t w_batch_stride,
+                       int32_t act, int32_t algo, void* stream) {
+  TMGCN_REQUIRE(R >= 0 && K > 0 && Nf > 0, "%s: bad shape R=%lld K=%d Nf=%d", who, (long long)R, K, Nf);
+  TMGCN_REQUIRE(algo == TMGCN_GEMM_AUTO || algo == TMGCN_GEMM_F32MFMA, "%s: unknown algo %d", who, algo);
+  TMGCN_REQUIRE(rows_per_batch >= 0, "%s: negative rows_per_batch", who);
+  TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "%s: unknown activation %d", who, act);
+  TMGCN_REQUIRE(!y_bf16 || (tmgcn_gemm_bf16y_supported(K, Nf) && !trans_w && !w_bf16 && algo == TMGCN_GEMM_AUTO),
+                "%s: K=%d, Nf=%d outside the bf16-Y kernels (Nf a multiple of 8 in [16,128]; K a multiple of 4 in "
+                "[16,128], or K < 16 with Nf <= 64; an fp32 W as it is stored, the default algorithm): use tmgcn_gemm_f32 "
+                "and a cast", who, K, Nf);
   if (R == 0) return TMGCN_OK;
-  TMGCN_REQUIRE(A && W && Y, "gemm: null pointer");
+  TMGCN_REQUIRE(A && W && Y, "%s: null pointer", who);
+  const bool small = use_small(K, Nf);
+  const int a_align = small ? 4 : 16;
+  TMGCN_REQUIRE(!y_bf16 || reinterpret_cast<uintptr_t>(A) % a_align == 0, "%s: A is not %d-byte aligned", who, a_align);
   hipStream_t st = (hipStream_t)stream;
-  GemmArgs a{A, static_cast<const float*>(W), Y, pre_act, R, K, Nf, trans_w, rows_per_batch, w_batch_stride,
-             act, 0, 0, nullptr, w_bf16 ? 1 : 0, 0, 0, 0, 0};
-  if (use_small(K, Nf)) {
+  GemmArgs a{A, static_cast<const float*>(W), static_cast<float*>(Y), pre_act, R, K, Nf, trans_w, rows_per_batch,
+             w_batch_stride, act, 0, 0, nullptr, w_bf16 ? 1 : 0, 0, 0, 0, 0};
+  const int64_t br = rows_per_batch ? rows_per_batch : R;
+  if (small) {  // thread per row
     const int Nfp = (Nf + 7) & ~7;
-    const int64_t br = rows_per_batch ? rows_per_batch : R;
     const int64_t max_w = (br >= 256 || !rows_per_batch) ? 2 : (256 / br + 2);  // a shared weight is one weight, however few rows
     size_t smem = (size_t)max_w * K * Nfp * sizeof(float);
-    TMGCN_REQUIRE(smem <= 64 * 1024, "gemm: per-slice weights too small a batch (%lld rows)",
-                  (long long)br);
+    TMGCN_REQUIRE(smem <= 64 * 1024, "%s: per-slice weights too small a batch (%lld rows)", who, (long long)br);
     if (Nfp <= 32 && smem + (size_t)256 * (Nfp + 1) * sizeof(float) <= 64 * 1024) {  // output tile through LDS: 256 rows x (Nfp + 1) floats, <= 33 KB; the launch stays within 64 KB of dynamic LDS
       a.stage_off = (int32_t)(smem / sizeof(float));
       smem += (size_t)256 * (Nfp + 1) * sizeof(float);
     }
     const unsigned grid = (unsigned)((R + 255) / 256);
-    hipLaunchKernelGGL(gemm_small_kernel<float>, dim3(grid), dim3(256), smem, st, a);
-    return check_launch("gemm_small");
+    void (*const kernel)(GemmArgs) = y_bf16 ? gemm_small_kernel<bf16_t> : gemm_small_kernel<float>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), smem, st, a);
+    return check_launch(y_bf16 ? "gemm_small (bf16 Y)" : "gemm_small");
   }
-  const int64_t br = rows_per_batch ? rows_per_batch : R;
   const int64_t nb = (R + br - 1) / br;
   a.tiles_per_batch = (br + BM - 1) / BM;
   a.n_tiles = nb * a.tiles_per_batch;
   const unsigned gy = (unsigned)((Nf + 127) / 128);
-  TMGCN_REQUIRE(a.n_tiles < (int64_t)0x7fffffff && gy <= 64, "gemm: shape too large for the tile scheduler");
-  const bool x3 = algo == TMGCN_GEMM_AUTO && K % 4 == 0 && K >= 16 && K <= 128 &&
-                  reinterpret_cast<uintptr_t>(A) % 16 == 0;
-  // 128 < K <= 512: the same kernel once per 128-wide k-chunk, every chunk after the first adding to
-  // Y (one more read of Y per chunk; still ~1.5-1.8x the exact-f32 MFMA kernel, which is compute-bound)
-  const bool x3_chunked = algo == TMGCN_GEMM_AUTO && K % 4 == 0 && K > 128 && K <= 512 &&
-                          reinterpret_cast<uintptr_t>(A) % 16 == 0;
-  if (x3_chunked) {
-    int64_t gx = w_bf16 ? persistent_grid(gemm_bf16x3_kernel<1, true>, 256) : persistent_grid(gemm_bf16x3_kernel<3, true>, 256);
+  TMGCN_REQUIRE(a.n_tiles < (int64_t)0x7fffffff && gy <= 64, "%s: shape too large for the tile scheduler", who);
+  // the split kernel: K a multiple of 4 in [16, 512], 128 < K as one launch per 128-wide k-chunk, every chunk after the
+  // first adding to Y (one more read of Y per chunk; still ~1.5-1.8x the exact-f32 MFMA kernel, which is compute-bound)
+  const bool x3 = algo == TMGCN_GEMM_AUTO && K % 4 == 0 && K >= 16 && K <= 512 && reinterpret_cast<uintptr_t>(A) % 16 == 0;
+  const bool chunked = K > 128;
+  TMGCN_REQUIRE(!y_bf16 || (x3 && !chunked), "%s: no kernel stores this product in bf16", who);  // held by the checks above
+  if (x3) {  // static persistent schedule: no tile counter
+    void (*const kernel)(GemmArgs) = y_bf16  ? gemm_bf16x3_kernel<3, false, bf16_t>
+                                     : chunked ? (w_bf16 ? gemm_bf16x3_kernel<1, true> : gemm_bf16x3_kernel<3, true>)
+                                               : (w_bf16 ? gemm_bf16x3_kernel<1> : gemm_bf16x3_kernel<3>);
+    int64_t gx = persistent_grid(kernel, 256);
     if (gx > a.n_tiles) gx = a.n_tiles;
     for (int k0 = 0; k0 < K; k0 += 128) {
       GemmArgs c = a;
-      const bool last = k0 + 128 >= K;
-      c.K = last ? K - k0 : 128;
-      c.lda = K;
-      c.k0 = k0;
-      c.accum = k0 > 0;
-      c.act = last ? act : TMGCN_ACT_NONE;
-      c.pre = last ? pre_act : nullptr;
-      if (w_bf16)
-        hipLaunchKernelGGL((gemm_bf16x3_kernel<1, true>), dim3((unsigned)gx, gy), dim3(256), 0, st, c);
-      else
-        hipLaunchKernelGGL((gemm_bf16x3_kernel<3, true>), dim3((unsigned)gx, gy), dim3(256), 0, st, c);
+      if (chunked) {
+        const bool last = k0 + 128 >= K;
+        c.K = last ? K - k0 : 128;
+        c.lda = K;
+        c.k0 = k0;
+        c.accum = k0 > 0;
+        c.act = last ? act : TMGCN_ACT_NONE;
+        c.pre = last ? pre_act : nullptr;
+      }
+      hipLaunchKernelGGL(kernel, dim3((unsigned)gx, gy), dim3(256), 0, st, c);
     }
-    return check_launch("gemm_bf16x3 (k-chunks)");
-  }
-  if (x3) {  // static persistent schedule: no tile counter
-    int64_t gx = w_bf16 ? persistent_grid(gemm_bf16x3_kernel<1>, 256) : persistent_grid(gemm_bf16x3_kernel<3>, 256);
-    if (gx > a.n_tiles) gx = a.n_tiles;
-    if (w_bf16)
-      hipLaunchKernelGGL(gemm_bf16x3_kernel<1>, dim3((unsigned)gx, gy), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL(gemm_bf16x3_kernel<3>, dim3((unsigned)gx, gy), dim3(256), 0, st, a);
-    return check_launch("gemm_bf16x3");
+    return check_launch(y_bf16 ? "gemm_bf16x3 (bf16 Y)" : chunked ? "gemm_bf16x3 (k-chunks)" : "gemm_bf16x3");
   }
   // gy consecutive counters of the pool (acquire zeroes one; take gy of them in a row)
   a.tile_counter = acquire_tile_counters(st, (int)gy);
-  TMGCN_REQUIRE(a.tile_counter, "gemm: no tile counters: %s", pool_error());
+  TMGCN_REQUIRE(a.tile_counter, "%s: no tile counters: %s", who, pool_error());
   int64_t gx = persistent_grid(gemm_mfma_kernel, 256);
   if (gx > a.n_tiles) gx = a.n_tiles;
   hipLaunchKernelGGL(gemm_mfma_kernel, dim3((unsigned)gx, gy), dim3(256), 0, st, a);
@@ -1460,14 +1462,43 @@ static int gemm_launch(const float* A, const void* W, bool w_bf16, float* Y, flo
 extern "C" int tmgcn_gemm_f32(const float* A, const float* W, float* Y, float* pre_act, int64_t R,
                                int32_t K, int32_t Nf, int32_t trans_w, int64_t rows_per_batch,
                                int64_t w_batch_stride, int32_t act, int32_t algo, void* stream) {
-  return gemm_launch(A, W, false, Y, pre_act, R, K, Nf, trans_w, rows_per_batch, w_batch_stride, act, algo, stream);
+  return gemm_launch("gemm", A, W, false, Y, false, pre_act, R, K, Nf, trans_w, rows_per_batch, w_batch_stride, act, algo,
+                     stream);
 }
 
 extern "C" int tmgcn_gemm_bf16w_f32(const float* A, const uint16_t* W_bf16, float* Y, float* pre_act, int64_t R,
                                      int32_t K, int32_t Nf, int32_t trans_w, int64_t rows_per_batch,
                                      int64_t w_batch_stride, int32_t act, int32_t algo, void* stream) {
-  return gemm_launch(A, W_bf16, true, Y, pre_act, R, K, Nf, trans_w, rows_per_batch, w_batch_stride, act, algo,
-                     stream);
+  return gemm_launch("gemm", A, W_bf16, true, Y, false, pre_act, R, K, Nf, trans_w, rows_per_batch, w_batch_stride, act,
+                     algo, stream);
+}
+
+// ---- the layer-1 GEMM of the bf16 activation path: Y stored in bf16, dW from a bf16 dY ---------------------------
+// The widths both directions have a kernel for: the output width is the K of the bf16 gather that reads Y (a multiple of
+// 8 in [16, 128]); the input width takes the split kernel (a multiple of 4 in [16, 128], one k-chunk) or, below 16, the
+// thread-per-row kernel (Nf <= 64).  dW then runs gemm_dw_bf16x3 / gemm_dw_small — never the narrow kernel (Nf >= 16).
+extern "C" int tmgcn_gemm_bf16y_supported(int32_t K, int32_t Nf) {
+  if (Nf < 16 || Nf > 128 || Nf % 8 != 0) return 0;
+  if (K >= 16) return (K <= 128 && K % 4 == 0) ? 1 : 0;
+  return (K >= 1 && Nf <= 64) ? 1 : 0;
+}
+
+extern "C" int tmgcn_gemm_bf16y(const float* A, const float* W, uint16_t* Y_bf16, float* pre_act, int64_t R, int32_t K,
+                                 int32_t Nf, int64_t rows_per_batch, int64_t w_batch_stride, int32_t act, void* stream) {
+  TMGCN_REQUIRE(w_batch_stride >= 0, "gemm_bf16y: negative w_batch_stride");
+  if (R > 0) {  // element alignment; what the kernels ask of A beyond it is gemm_launch's to check
+    TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(W) % 4 == 0, "gemm_bf16y: W is not 4-byte aligned");
+    TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(Y_bf16) % 2 == 0, "gemm_bf16y: Y is not 2-byte aligned");
+    TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(pre_act) % 4 == 0, "gemm_bf16y: pre_act is not 4-byte aligned");
+  }
+  if (act == TMGCN_ACT_NONE) pre_act = nullptr;  // the pre-activation is stored beside an activation only
+  return gemm_launch("gemm_bf16y", A, W, false, Y_bf16, true, pre_act, R, K, Nf, 0, rows_per_batch, w_batch_stride, act,
+                     TMGCN_GEMM_AUTO, stream);
+}
+
+// block slabs + the group slabs of slab_tree_finish
+static int64_t dw_workspace_bytes(int64_t nb, int chunks, int32_t K, int32_t Nf) {
+  return (nb * chunks + kSyncGroups) * (int64_t)K * Nf * (int64_t)sizeof(float);
 }
 
 extern "C" int64_t tmgcn_gemm_dw_workspace_bytes(int64_t R, int32_t K, int32_t Nf,
@@ -1476,7 +1507,7 @@ extern "C" int64_t tmgcn_gemm_dw_workspace_bytes(int64_t R, int32_t K, int32_t N
   int64_t nb, rpc;
   int chunks;
   dw_plan(R, rows_per_batch, &nb, &chunks, &rpc);
-  return (nb * chunks + kSyncGroups) * (int64_t)K * Nf * (int64_t)sizeof(float);      // block slabs + the group slabs of slab_tree_finish
+  return dw_workspace_bytes(nb, chunks, K, Nf);
 }
 
 // the fixed-order sum of the row-chunk slabs of a dW launch into dW
@@ -1492,32 +1523,32 @@ static int dw_reduce_launch(const void* workspace, float* dW, int64_t nb, int32_
   return check_launch("gemm_dw_reduce");
 }
 
-static int gemm_dw_launch(const float* A, const float* dY, const float* pre, int32_t act, float* dW, int64_t R, int32_t K,
-                          int32_t Nf, int64_t rows_per_batch, int32_t algo, void* workspace, int64_t workspace_bytes,
-                          void* stream) {
-  TMGCN_REQUIRE(R >= 0 && K > 0 && Nf > 0, "gemm_dw: bad shape");
-  TMGCN_REQUIRE(algo == TMGCN_DW_AUTO || algo == TMGCN_DW_F32MFMA, "gemm_dw: unknown algo %d", algo);
-  TMGCN_REQUIRE(rows_per_batch >= 0, "gemm_dw: negative rows_per_batch");
-  TMGCN_REQUIRE(dW, "gemm_dw: null dW");
+// The one dW launcher.  dym: how dY is stored and whether act'(pre) multiplies it as it is loaded (DY_F32: an fp32 dY;
+// DY_BF16 / DY_BF16_ACT: a bf16 dY, tmgcn_gemm_dw_act_bf16).  The bf16 modes exist in gemm_dw_small and gemm_dw_bf16x3
+// only: they never take the narrow kernel, and what would need gemm_dw_lds is refused.  For an fp32 dY a `pre` asks for
+// the narrow kernel's own fold of act' (tmgcn_gemm_dw_act_f32).
+static int gemm_dw_launch(const char* who, const float* A, const void* dY, int dym, const float* pre, int32_t act, float* dW,
+                          int64_t R, int32_t K, int32_t Nf, int64_t rows_per_batch, int32_t algo, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  TMGCN_REQUIRE(R >= 0 && K > 0 && Nf > 0, "%s: bad shape R=%lld K=%d Nf=%d", who, (long long)R, K, Nf);
+  TMGCN_REQUIRE(algo == TMGCN_DW_AUTO || algo == TMGCN_DW_F32MFMA, "%s: unknown algo %d", who, algo);
+  TMGCN_REQUIRE(rows_per_batch >= 0, "%s: negative rows_per_batch", who);
+  TMGCN_REQUIRE(dW, "%s: null dW", who);
   hipStream_t st = (hipStream_t)stream;
   int64_t nb, rpc;
   int chunks;
   dw_plan(R, rows_per_batch, &nb, &chunks, &rpc);
-  if (R == 0) {
+  if (R == 0) {  // the fp32 entries: dW = 0.  tmgcn_gemm_dw_act_bf16 returns before it gets here and leaves dW as it is
     (void)hipMemsetAsync(dW, 0, (size_t)K * Nf * sizeof(float), st);
     return check_launch("gemm_dw memset");
   }
-  TMGCN_REQUIRE(A && dY, "gemm_dw: null pointer");
-  const int64_t need = (nb * chunks + kSyncGroups) * (int64_t)K * Nf * (int64_t)sizeof(float);
-  if (!workspace || workspace_bytes < need) {
-    set_error("gemm_dw: workspace %lld B < required %lld B", (long long)workspace_bytes,
-              (long long)need);
-    return TMGCN_ERR_WORKSPACE;
-  }
-  const bool narrow = K % 2 == 0 && Nf % 2 == 0 && K <= 8 && Nf <= 8 && reinterpret_cast<uintptr_t>(A) % 8 == 0 &&
-                      reinterpret_cast<uintptr_t>(dY) % 8 == 0;
-  TMGCN_REQUIRE(!pre || narrow, "gemm_dw_act: the fused activation gradient needs the narrow kernel (even K, Nf <= 8, 8-byte "
-                                 "aligned operands); use tmgcn_act_bwd_f32 + tmgcn_gemm_dw_f32");
+  TMGCN_REQUIRE(A && dY, "%s: null pointer", who);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, dw_workspace_bytes(nb, chunks, K, Nf))) return rc;
+  const bool narrow = dym == DY_F32 && K % 2 == 0 && Nf % 2 == 0 && K <= 8 && Nf <= 8 &&
+                      reinterpret_cast<uintptr_t>(A) % 8 == 0 && reinterpret_cast<uintptr_t>(dY) % 8 == 0;
+  TMGCN_REQUIRE(dym != DY_F32 || !pre || narrow,
+                "%s: the fused activation gradient needs the narrow kernel (even K, Nf <= 8, 8-byte aligned operands); use "
+                "tmgcn_act_bwd_f32 + tmgcn_gemm_dw_f32", who);
   if (narrow) {
     // The narrow kernel's fixed costs are per block (the K·Nf-value block reduction, the slab and the hand-off tickets),
     // its loop is a stream: about two blocks per CU while the operand is small (captured steps, kernel durations under
@@ -1534,15 +1565,15 @@ static int gemm_dw_launch(const float* A, const float* dY, const float* pre, int
       chunks = (int)((br + rpc - 1) / rpc);
     }
   }
-  DwArgs a{A, dY, (float*)workspace, R, K, Nf, rows_per_batch ? rows_per_batch : R, chunks, rpc};
+  DwArgs a{A, static_cast<const float*>(dY), (float*)workspace, R, K, Nf, rows_per_batch ? rows_per_batch : R, chunks, rpc};
+  a.pre = pre;
+  a.act = act;
   const unsigned gx = (unsigned)(nb * chunks);
   if (narrow) {
     a.dW = dW;
-    a.pre = pre;
-    a.act = act;
     a.n_batch = (int32_t)nb;
     a.sync = acquire_sync_word(st);
-    TMGCN_REQUIRE(a.sync, "gemm_dw: no hand-off block: %s", pool_error());
+    TMGCN_REQUIRE(a.sync, "%s: no hand-off block: %s", who, pool_error());
 #define TMGCN_DWN_L(KT_, NT_)                                                                          \
   if (pre) hipLaunchKernelGGL((gemm_dw_narrow_kernel<KT_, NT_, true>), dim3(gx), dim3(256), 0, st, a); \
   else hipLaunchKernelGGL((gemm_dw_narrow_kernel<KT_, NT_, false>), dim3(gx), dim3(256), 0, st, a);
@@ -1562,27 +1593,32 @@ static int gemm_dw_launch(const float* A, const float* dY, const float* pre, int
 #undef TMGCN_DWN_N
 #undef TMGCN_DWN_L
     return check_launch("gemm_dw_narrow");          // reduced by its own last block
-  } else if (use_small(K, Nf)) {
-    const size_t smem = (size_t)DW_ROWS * (K + Nf) * sizeof(float);
-    hipLaunchKernelGGL(gemm_dw_small_kernel<DY_F32>, dim3(gx), dim3(256), smem, st, a);
+  }
+  if (use_small(K, Nf)) {
+    void (*const kernel)(DwArgs) = dym == DY_F32    ? gemm_dw_small_kernel<DY_F32>
+                                   : dym == DY_BF16 ? gemm_dw_small_kernel<DY_BF16>
+                                                    : gemm_dw_small_kernel<DY_BF16_ACT>;
+    hipLaunchKernelGGL(kernel, dim3(gx), dim3(256), (size_t)DW_ROWS * (K + Nf) * sizeof(float), st, a);
   } else {
     const unsigned gy = (unsigned)(((K + 127) / 128) * ((Nf + 127) / 128));
-    const bool x3 = algo == TMGCN_DW_AUTO && K % 4 == 0 && Nf % 4 == 0 &&
-                    reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(dY) % 16 == 0;
-    if (x3)
-      hipLaunchKernelGGL(gemm_dw_bf16x3_kernel<DY_F32>, dim3(gx, gy), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL(gemm_dw_lds_kernel, dim3(gx, gy), dim3(256), 0, st, a);
+    const bool x3 = algo == TMGCN_DW_AUTO && K % 4 == 0 && Nf % 4 == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(dY) % (dym == DY_F32 ? 16 : 8) == 0;
+    TMGCN_REQUIRE(x3 || dym == DY_F32, "%s: no kernel reads this bf16 dY", who);  // held by tmgcn_gemm_dw_act_bf16's checks
+    void (*const kernel)(DwArgs) = !x3               ? gemm_dw_lds_kernel
+                                   : dym == DY_F32   ? gemm_dw_bf16x3_kernel<DY_F32>
+                                   : dym == DY_BF16 ? gemm_dw_bf16x3_kernel<DY_BF16>
+                                                     : gemm_dw_bf16x3_kernel<DY_BF16_ACT>;
+    hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(256), 0, st, a);
   }
-  int rc = check_launch("gemm_dw");
-  if (rc) return rc;
+  if (int rc = check_launch(who)) return rc;
   return dw_reduce_launch(workspace, dW, nb, K, Nf, chunks, st);
 }
 
 extern "C" int tmgcn_gemm_dw_f32(const float* A, const float* dY, float* dW, int64_t R, int32_t K, int32_t Nf,
                                   int64_t rows_per_batch, int32_t algo, void* workspace, int64_t workspace_bytes,
                                   void* stream) {
-  return gemm_dw_launch(A, dY, nullptr, TMGCN_ACT_NONE, dW, R, K, Nf, rows_per_batch, algo, workspace, workspace_bytes, stream);
+  return gemm_dw_launch("gemm_dw", A, dY, DY_F32, nullptr, TMGCN_ACT_NONE, dW, R, K, Nf, rows_per_batch, algo, workspace,
+                        workspace_bytes, stream);
 }
 
 extern "C" int tmgcn_gemm_dw_act_supported(int32_t K, int32_t Nf) {
@@ -1595,106 +1631,27 @@ extern "C" int tmgcn_gemm_dw_act_f32(const float* A, const float* dY, const floa
   TMGCN_REQUIRE(tmgcn_gemm_dw_act_supported(K, Nf), "gemm_dw_act: even K, Nf <= 8 only (got %d x %d)", K, Nf);
   TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "gemm_dw_act: unknown activation %d", act);
   TMGCN_REQUIRE(pre_act && reinterpret_cast<uintptr_t>(pre_act) % 8 == 0, "gemm_dw_act: pre_act must be given, 8-byte aligned");
-  return gemm_dw_launch(A, dY, pre_act, act, dW, R, K, Nf, rows_per_batch, TMGCN_DW_AUTO, workspace, workspace_bytes, stream);
-}
-
-// ---- the layer-1 GEMM of the bf16 activation path: Y stored in bf16, dW from a bf16 dY ---------------------------
-// The widths both directions have a kernel for: the output width is the K of the bf16 gather that reads Y (a multiple of
-// 8 in [16, 128]); the input width takes the split kernel (a multiple of 4 in [16, 128], one k-chunk) or, below 16, the
-// thread-per-row kernel (Nf <= 64).  dW then runs gemm_dw_bf16x3 / gemm_dw_small — never the narrow kernel (Nf >= 16).
-extern "C" int tmgcn_gemm_bf16y_supported(int32_t K, int32_t Nf) {
-  if (Nf < 16 || Nf > 128 || Nf % 8 != 0) return 0;
-  if (K >= 16) return (K <= 128 && K % 4 == 0) ? 1 : 0;
-  return (K >= 1 && Nf <= 64) ? 1 : 0;
-}
-
-extern "C" int tmgcn_gemm_bf16y(const float* A, const float* W, uint16_t* Y_bf16, float* pre_act, int64_t R, int32_t K,
-                                 int32_t Nf, int64_t rows_per_batch, int64_t w_batch_stride, int32_t act, void* stream) {
-  TMGCN_REQUIRE(R >= 0 && K > 0 && Nf > 0, "gemm_bf16y: bad shape R=%lld K=%d Nf=%d", (long long)R, K, Nf);
-  TMGCN_REQUIRE(rows_per_batch >= 0 && w_batch_stride >= 0, "gemm_bf16y: negative rows_per_batch / w_batch_stride");
-  TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "gemm_bf16y: unknown activation %d", act);
-  TMGCN_REQUIRE(tmgcn_gemm_bf16y_supported(K, Nf),
-                "gemm_bf16y: K=%d, Nf=%d outside the bf16-Y kernels (Nf a multiple of 8 in [16,128]; K a multiple of 4 in "
-                "[16,128], or K < 16 with Nf <= 64): use tmgcn_gemm_f32 and a cast", K, Nf);
-  if (R == 0) return TMGCN_OK;
-  TMGCN_REQUIRE(A && W && Y_bf16, "gemm_bf16y: null pointer");
-  const bool small = use_small(K, Nf);
-  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(A) % (small ? 4 : 16) == 0, "gemm_bf16y: A is not %d-byte aligned", small ? 4 : 16);
-  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(W) % 4 == 0, "gemm_bf16y: W is not 4-byte aligned");
-  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(Y_bf16) % 2 == 0, "gemm_bf16y: Y is not 2-byte aligned");
-  TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(pre_act) % 4 == 0, "gemm_bf16y: pre_act is not 4-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (act == TMGCN_ACT_NONE) pre_act = nullptr;  // as tmgcn_gemm_f32: the pre-activation is stored beside an activation only
-  GemmArgs a{A, W, reinterpret_cast<float*>(Y_bf16), pre_act, R, K, Nf, 0, rows_per_batch, w_batch_stride,
-             act, 0, 0, nullptr, 0, 0, 0, 0, 0};
-  const int64_t br = rows_per_batch ? rows_per_batch : R;
-  if (small) {  // the plan of gemm_launch
-    const int Nfp = (Nf + 7) & ~7;
-    const int64_t max_w = (br >= 256 || !rows_per_batch) ? 2 : (256 / br + 2);
-    size_t smem = (size_t)max_w * K * Nfp * sizeof(float);
-    TMGCN_REQUIRE(smem <= 64 * 1024, "gemm_bf16y: per-slice weights too small a batch (%lld rows)", (long long)br);
-    if (Nfp <= 32 && smem + (size_t)256 * (Nfp + 1) * sizeof(float) <= 64 * 1024) {
-      a.stage_off = (int32_t)(smem / sizeof(float));
-      smem += (size_t)256 * (Nfp + 1) * sizeof(float);
-    }
-    hipLaunchKernelGGL(gemm_small_kernel<bf16_t>, dim3((unsigned)((R + 255) / 256)), dim3(256), smem, st, a);
-    return check_launch("gemm_small (bf16 Y)");
-  }
-  const int64_t nb = (R + br - 1) / br;
-  a.tiles_per_batch = (br + BM - 1) / BM;
-  a.n_tiles = nb * a.tiles_per_batch;
-  TMGCN_REQUIRE(a.n_tiles < (int64_t)0x7fffffff, "gemm_bf16y: shape too large for the tile scheduler");
-  int64_t gx = persistent_grid(gemm_bf16x3_kernel<3, false, bf16_t>, 256);
-  if (gx > a.n_tiles) gx = a.n_tiles;
-  hipLaunchKernelGGL((gemm_bf16x3_kernel<3, false, bf16_t>), dim3((unsigned)gx, 1), dim3(256), 0, st, a);
-  return check_launch("gemm_bf16x3 (bf16 Y)");
+  return gemm_dw_launch("gemm_dw_act", A, dY, DY_F32, pre_act, act, dW, R, K, Nf, rows_per_batch, TMGCN_DW_AUTO, workspace,
+                        workspace_bytes, stream);
 }
 
 extern "C" int tmgcn_gemm_dw_act_bf16(const float* A, const uint16_t* dY_bf16, const float* pre_act, int32_t act, float* dW,
                                        int64_t R, int32_t K, int32_t Nf, int64_t rows_per_batch, void* workspace,
                                        int64_t workspace_bytes, void* stream) {
-  TMGCN_REQUIRE(R >= 0 && K > 0 && Nf > 0, "gemm_dw_act_bf16: bad shape R=%lld K=%d Nf=%d", (long long)R, K, Nf);
-  TMGCN_REQUIRE(rows_per_batch >= 0, "gemm_dw_act_bf16: negative rows_per_batch");
   TMGCN_REQUIRE(act >= TMGCN_ACT_NONE && act <= TMGCN_ACT_SELU, "gemm_dw_act_bf16: unknown activation %d", act);
+  TMGCN_REQUIRE(rows_per_batch >= 0, "gemm_dw_act_bf16: negative rows_per_batch");
   TMGCN_REQUIRE(tmgcn_gemm_bf16y_supported(K, Nf),
                 "gemm_dw_act_bf16: K=%d, Nf=%d outside the bf16-dY kernels (tmgcn_gemm_bf16y_supported): widen dY and use "
                 "tmgcn_act_bwd_f32 + tmgcn_gemm_dw_f32", K, Nf);
-  if (R == 0) return TMGCN_OK;  // no rows: nothing is launched and dW is left as it is
-  TMGCN_REQUIRE(A && dY_bf16 && dW, "gemm_dw_act_bf16: null pointer");
-  TMGCN_REQUIRE(act == TMGCN_ACT_NONE || pre_act, "gemm_dw_act_bf16: act=%d needs pre_act", act);
+  if (R == 0) return TMGCN_OK;  // no rows: nothing is launched and dW is left as it is (the fp32 entries zero-fill it)
+  const bool with_act = act != TMGCN_ACT_NONE;
+  TMGCN_REQUIRE(!with_act || pre_act, "gemm_dw_act_bf16: act=%d needs pre_act", act);
   const bool small = use_small(K, Nf);
   TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(A) % (small ? 4 : 16) == 0, "gemm_dw_act_bf16: A is not %d-byte aligned", small ? 4 : 16);
   TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(dY_bf16) % (small ? 2 : 8) == 0, "gemm_dw_act_bf16: dY is not %d-byte aligned", small ? 2 : 8);
-  TMGCN_REQUIRE(act == TMGCN_ACT_NONE || reinterpret_cast<uintptr_t>(pre_act) % (small ? 4 : 16) == 0,
+  TMGCN_REQUIRE(!with_act || reinterpret_cast<uintptr_t>(pre_act) % (small ? 4 : 16) == 0,
                 "gemm_dw_act_bf16: pre_act is not %d-byte aligned", small ? 4 : 16);
   TMGCN_REQUIRE(reinterpret_cast<uintptr_t>(dW) % 4 == 0, "gemm_dw_act_bf16: dW is not 4-byte aligned");
-  int64_t nb, rpc;
-  int chunks;
-  dw_plan(R, rows_per_batch, &nb, &chunks, &rpc);
-  const int64_t need = (nb * chunks + kSyncGroups) * (int64_t)K * Nf * (int64_t)sizeof(float);
-  if (!workspace || workspace_bytes < need) {
-    set_error("gemm_dw_act_bf16: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-    return TMGCN_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  DwArgs a{A, reinterpret_cast<const float*>(dY_bf16), (float*)workspace, R, K, Nf, rows_per_batch ? rows_per_batch : R, chunks, rpc};
-  const bool with_act = act != TMGCN_ACT_NONE;
-  a.pre = with_act ? pre_act : nullptr;
-  a.act = act;
-  const unsigned gx = (unsigned)(nb * chunks);
-  if (small) {
-    const size_t smem = (size_t)DW_ROWS * (K + Nf) * sizeof(float);
-    if (with_act)
-      hipLaunchKernelGGL(gemm_dw_small_kernel<DY_BF16_ACT>, dim3(gx), dim3(256), smem, st, a);
-    else
-      hipLaunchKernelGGL(gemm_dw_small_kernel<DY_BF16>, dim3(gx), dim3(256), smem, st, a);
-  } else {  // K, Nf <= 128: one 128 x 128 output tile
-    if (with_act)
-      hipLaunchKernelGGL(gemm_dw_bf16x3_kernel<DY_BF16_ACT>, dim3(gx, 1), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL(gemm_dw_bf16x3_kernel<DY_BF16>, dim3(gx, 1), dim3(256), 0, st, a);
-  }
-  int rc = check_launch("gemm_dw_act_bf16");
-  if (rc) return rc;
-  return dw_reduce_launch(workspace, dW, nb, K, Nf, chunks, st);
+  return gemm_dw_launch("gemm_dw_act_bf16", A, dY_bf16, with_act ? DY_BF16_ACT : DY_BF16, with_act ? pre_act : nullptr, act, dW,
+                        R, K, Nf, rows_per_batch, TMGCN_DW_AUTO, workspace, workspace_bytes, stream);
 }

@@ -53,13 +53,15 @@ inline void* ptr(const Tensor& t) {
 inline void* stream_of(const Tensor& t) {
   return (void*)c10::hip::getCurrentHIPStream(t.device().index()).stream();
 }
-inline void want(const Tensor& t, const char* name, at::ScalarType dt = at::kFloat) {
-  TORCH_CHECK(t.defined(), name, ": undefined tensor");
-  TORCH_CHECK(t.is_cuda(), name, ": expected a ROCm (cuda) tensor, got device ", t.device(),
+// `who` `name`: the operator (where several share a body) and the operand, as the message names them
+inline void want(const Tensor& t, const char* who, const char* name, at::ScalarType dt) {
+  TORCH_CHECK(t.defined(), who, name, ": undefined tensor");
+  TORCH_CHECK(t.is_cuda(), who, name, ": expected a ROCm (cuda) tensor, got device ", t.device(),
               "; the TM-GCN layer has no CPU path");
-  TORCH_CHECK(t.scalar_type() == dt, name, ": expected dtype ", dt, ", got ", t.scalar_type());
-  TORCH_CHECK(t.is_contiguous(), name, ": expected a contiguous tensor");
+  TORCH_CHECK(t.scalar_type() == dt, who, name, ": expected dtype ", dt, ", got ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), who, name, ": expected a contiguous tensor");
 }
+inline void want(const Tensor& t, const char* name, at::ScalarType dt = at::kFloat) { want(t, "", name, dt); }
 inline void ok(int rc, const char* what) {
   TORCH_CHECK(rc == 0, what, " failed (status ", rc, "): ", tmgcn_last_error());
 }
@@ -74,26 +76,50 @@ inline bool has(const Tensor& t) { return t.defined() && t.numel() > 0; }
 // ---------------------------------------------------------------------------------------
 // kernel-level operators
 // ---------------------------------------------------------------------------------------
-Tensor mtransform(const Tensor& M, const Tensor& X, bool transpose, int64_t row_off, int64_t col_off,
-                  int64_t T_out, int64_t band_lo, int64_t band_hi, int64_t x_group_rows,
-                  int64_t y_group_rows) {
-  want(M, "mtransform M");
-  want(X, "mtransform X");
-  TORCH_CHECK(M.dim() == 2 && M.size(0) == M.size(1), "mtransform: M must be square");
-  TORCH_CHECK(X.dim() >= 1, "mtransform: X needs a leading time mode");
+// One body behind mtransform and mtransform_bf16.  bf16: the band kernel of csrc/mtransform_bf16.hip, X fp32 or bf16, Y
+// allocated in bf16 (out_bf16) or fp32, the cast folded into the load / the store; else tmgcn_mtransform_f32, the only
+// one with grouped rows (xg, yg).
+static Tensor mtransform_any(const char* who, bool bf16, const Tensor& M, const Tensor& X, bool transpose, int64_t row_off,
+                             int64_t col_off, int64_t T_out, int64_t band_lo, int64_t band_hi, bool out_bf16, int64_t xg,
+                             int64_t yg) {
+  want(M, who, " M", at::kFloat);
+  const bool x_bf16 = bf16 && X.defined() && X.scalar_type() == at::kBFloat16;
+  want(X, who, " X", x_bf16 ? at::kBFloat16 : at::kFloat);
+  TORCH_CHECK(M.dim() == 2 && M.size(0) == M.size(1), who, ": M must be square");
+  TORCH_CHECK(X.dim() >= 1, who, ": X needs a leading time mode");
   c10::DeviceGuard g(X.device());
   const int64_t T_in = X.size(0);
   if (T_out < 0) T_out = T_in;
   const int64_t C = T_in ? X.numel() / T_in : 0;
   auto sizes = X.sizes().vec();
   sizes[0] = T_out;
-  Tensor Y = at::empty(sizes, X.options());
-  ok(tmgcn_mtransform_f32((const float*)ptr(M), (int32_t)M.size(0), (int32_t)M.size(0), transpose ? 1 : 0,
-                          (int32_t)row_off, (int32_t)col_off, (int32_t)T_out, (int32_t)T_in,
-                          (int32_t)band_lo, (int32_t)band_hi, (const float*)ptr(X), (float*)ptr(Y), C,
-                          (int32_t)x_group_rows, (int32_t)y_group_rows, stream_of(X)),
-     "tmgcn_mtransform_f32");
+  Tensor Y = at::empty(sizes, X.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+  const int32_t n = (int32_t)M.size(0);
+  if (bf16)
+    ok(tmgcn_mtransform_bf16((const float*)ptr(M), n, n, transpose ? 1 : 0, (int32_t)row_off, (int32_t)col_off, (int32_t)T_out,
+                             (int32_t)T_in, (int32_t)band_lo, (int32_t)band_hi, ptr(X), x_bf16 ? 1 : 0, ptr(Y), out_bf16 ? 1 : 0,
+                             C, stream_of(X)),
+       "tmgcn_mtransform_bf16");
+  else
+    ok(tmgcn_mtransform_f32((const float*)ptr(M), n, n, transpose ? 1 : 0, (int32_t)row_off, (int32_t)col_off, (int32_t)T_out,
+                            (int32_t)T_in, (int32_t)band_lo, (int32_t)band_hi, (const float*)ptr(X), (float*)ptr(Y), C,
+                            (int32_t)xg, (int32_t)yg, stream_of(X)),
+       "tmgcn_mtransform_f32");
   return Y;
+}
+Tensor mtransform(const Tensor& M, const Tensor& X, bool transpose, int64_t row_off, int64_t col_off,
+                  int64_t T_out, int64_t band_lo, int64_t band_hi, int64_t x_group_rows,
+                  int64_t y_group_rows) {
+  return mtransform_any("mtransform", false, M, X, transpose, row_off, col_off, T_out, band_lo, band_hi, false, x_group_rows,
+                        y_group_rows);
+}
+// X and / or Y stored in bf16, one launch; an fp32 X with an fp32 Y is tmgcn::mtransform
+Tensor mtransform_bf16(const Tensor& M, const Tensor& X, bool transpose, int64_t row_off, int64_t col_off, int64_t T_out,
+                       int64_t band_lo, int64_t band_hi, bool out_bf16) {
+  return mtransform_any("mtransform_bf16", true, M, X, transpose, row_off, col_off, T_out, band_lo, band_hi, out_bf16, 0, 0);
+}
+bool mtransform_bf16_supported(int64_t band_lo, int64_t band_hi) {
+  return band_lo <= INT32_MAX && band_hi <= INT32_MAX && tmgcn_mtransform_bf16_supported((int32_t)band_lo, (int32_t)band_hi) != 0;
 }
 
 // Column-window form: X [T_in, n, F] and Y [T_out, n, F] may be views whose slices are further apart
@@ -123,32 +149,6 @@ void mtransform_out(const Tensor& M, const Tensor& X, Tensor Y, bool transpose, 
                              (int32_t)band_hi, (const float*)ptr(X), ldx, (float*)ptr(Y), ldy, C, (int32_t)x_group_rows,
                              (int32_t)y_group_rows, stream_of(X)),
      "tmgcn_mtransform_ld_f32");
-}
-
-// The band M-transform with X and / or Y stored in bf16 (csrc/mtransform_bf16.hip): X fp32 or bf16, Y allocated in bf16
-// (out_bf16) or fp32; one launch, the cast folded into the load / the store.  An fp32 X with an fp32 Y is tmgcn::mtransform.
-bool mtransform_bf16_supported(int64_t band_lo, int64_t band_hi) {
-  return band_lo <= INT32_MAX && band_hi <= INT32_MAX && tmgcn_mtransform_bf16_supported((int32_t)band_lo, (int32_t)band_hi) != 0;
-}
-Tensor mtransform_bf16(const Tensor& M, const Tensor& X, bool transpose, int64_t row_off, int64_t col_off, int64_t T_out,
-                       int64_t band_lo, int64_t band_hi, bool out_bf16) {
-  want(M, "mtransform_bf16 M");
-  const bool x_bf16 = X.defined() && X.scalar_type() == at::kBFloat16;
-  want(X, "mtransform_bf16 X", x_bf16 ? at::kBFloat16 : at::kFloat);
-  TORCH_CHECK(M.dim() == 2 && M.size(0) == M.size(1), "mtransform_bf16: M must be square");
-  TORCH_CHECK(X.dim() >= 1, "mtransform_bf16: X needs a leading time mode");
-  c10::DeviceGuard g(X.device());
-  const int64_t T_in = X.size(0);
-  if (T_out < 0) T_out = T_in;
-  const int64_t C = T_in ? X.numel() / T_in : 0;
-  auto sizes = X.sizes().vec();
-  sizes[0] = T_out;
-  Tensor Y = at::empty(sizes, X.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
-  ok(tmgcn_mtransform_bf16((const float*)ptr(M), (int32_t)M.size(0), (int32_t)M.size(0), transpose ? 1 : 0, (int32_t)row_off,
-                           (int32_t)col_off, (int32_t)T_out, (int32_t)T_in, (int32_t)band_lo, (int32_t)band_hi, ptr(X),
-                           x_bf16 ? 1 : 0, ptr(Y), out_bf16 ? 1 : 0, C, stream_of(X)),
-     "tmgcn_mtransform_bf16");
-  return Y;
 }
 
 void check_csr(const Tensor& rowptr, const Tensor& col, const Tensor& val, const Tensor& X, int64_t N,
@@ -284,65 +284,96 @@ void spmm_gemm_out(const Tensor& rowptr, const Tensor& col, const Tensor& val, c
                    giant_chunks);
 }
 
-std::tuple<Tensor, Tensor> bgemm(const Tensor& A, const Tensor& W, bool trans_w, int64_t act, bool want_pre,
-                                 int64_t algo) {
-  want(A, "gemm A");
-  const bool w_bf16 = W.defined() && W.scalar_type() == at::kBFloat16;  // a parameter stored in bf16
-  want(W, "gemm W", w_bf16 ? at::kBFloat16 : at::kFloat);
-  TORCH_CHECK(A.dim() == 3, "gemm: A must be [T,N,K]");
+// One body behind bgemm and gemm_bf16y: A [T,N,K] fp32, W [K,Nf] shared or [T,K,Nf] per slice; returns Y and the fp32
+// pre-activation (want_pre and an activation).  y_bf16: act(A·W) stored in bf16 by the GEMM itself (tmgcn_gemm_bf16y: an fp32
+// W as it is stored, the default algorithm), bit for bit the fp32 Y through round_bf16; else W may be a bf16 parameter.
+static std::tuple<Tensor, Tensor> gemm_any(const char* who, bool y_bf16, const Tensor& A, const Tensor& W, bool trans_w,
+                                           int64_t act, bool want_pre, int64_t algo) {
+  want(A, who, " A", at::kFloat);
+  const bool w_bf16 = !y_bf16 && W.defined() && W.scalar_type() == at::kBFloat16;  // a parameter stored in bf16
+  want(W, who, " W", w_bf16 ? at::kBFloat16 : at::kFloat);
+  TORCH_CHECK(A.dim() == 3, who, ": A must be [T,N,K]");
   c10::DeviceGuard g(A.device());
   const int64_t T = A.size(0), N = A.size(1), K = A.size(2);
-  const WShape s = w_shape(W, trans_w, T, K, "gemm");
-  Tensor Y = at::empty({T, N, s.wn}, A.options());
-  Tensor pre = (want_pre && act != TMGCN_ACT_NONE) ? at::empty_like(Y) : Tensor();
-  if (w_bf16)
+  const WShape s = w_shape(W, trans_w, T, K, who);
+  Tensor Y = at::empty({T, N, s.wn}, A.options().dtype(y_bf16 ? at::kBFloat16 : at::kFloat));
+  Tensor pre = (want_pre && act != TMGCN_ACT_NONE) ? at::empty({T, N, s.wn}, A.options()) : Tensor();
+  const int64_t rpb = s.per_slice ? N : 0;
+  if (y_bf16)
+    ok(tmgcn_gemm_bf16y((const float*)ptr(A), (const float*)ptr(W), (uint16_t*)ptr(Y), (float*)ptr(pre), T * N, (int32_t)K,
+                        (int32_t)s.wn, rpb, s.stride, (int32_t)act, stream_of(A)),
+       "tmgcn_gemm_bf16y");
+  else if (w_bf16)
     ok(tmgcn_gemm_bf16w_f32((const float*)ptr(A), (const uint16_t*)ptr(W), (float*)ptr(Y), (float*)ptr(pre), T * N,
-                            (int32_t)K, (int32_t)s.wn, trans_w ? 1 : 0, s.per_slice ? N : 0, s.stride,
-                            (int32_t)act, (int32_t)algo, stream_of(A)),
+                            (int32_t)K, (int32_t)s.wn, trans_w ? 1 : 0, rpb, s.stride, (int32_t)act, (int32_t)algo,
+                            stream_of(A)),
        "tmgcn_gemm_bf16w_f32");
   else
-    ok(tmgcn_gemm_f32((const float*)ptr(A), (const float*)ptr(W), (float*)ptr(Y), (float*)ptr(pre), T * N,
-                      (int32_t)K, (int32_t)s.wn, trans_w ? 1 : 0, s.per_slice ? N : 0, s.stride, (int32_t)act,
-                      (int32_t)algo, stream_of(A)),
+    ok(tmgcn_gemm_f32((const float*)ptr(A), (const float*)ptr(W), (float*)ptr(Y), (float*)ptr(pre), T * N, (int32_t)K,
+                      (int32_t)s.wn, trans_w ? 1 : 0, rpb, s.stride, (int32_t)act, (int32_t)algo, stream_of(A)),
        "tmgcn_gemm_f32");
   return {Y, pre.defined() ? pre : none_like(A)};
 }
+std::tuple<Tensor, Tensor> bgemm(const Tensor& A, const Tensor& W, bool trans_w, int64_t act, bool want_pre,
+                                 int64_t algo) {
+  return gemm_any("gemm", false, A, W, trans_w, act, want_pre, algo);
+}
+std::tuple<Tensor, Tensor> gemm_bf16y(const Tensor& A, const Tensor& W, int64_t act, bool want_pre) {
+  return gemm_any("gemm_bf16y", true, A, W, false, act, want_pre, TMGCN_GEMM_AUTO);
+}
+bool gemm_bf16y_supported(int64_t K, int64_t Nf) {
+  return K >= 0 && Nf >= 0 && K <= INT32_MAX && Nf <= INT32_MAX && tmgcn_gemm_bf16y_supported((int32_t)K, (int32_t)Nf) != 0;
+}
 
-Tensor bgemm_dW(const Tensor& A, const Tensor& dY, bool per_slice, int64_t algo) {
-  want(A, "gemm_dw A");
-  want(dY, "gemm_dw dY");
-  TORCH_CHECK(A.dim() == 3 && dY.dim() == 3 && A.size(0) == dY.size(0) && A.size(1) == dY.size(1),
-              "gemm_dw: A ", A.sizes(), " and dY ", dY.sizes(), " do not match");
+// One body behind bgemm_dW, bgemm_dW_act and gemm_dw_act_bf16: dW = Aᵀ·dY, shared ([K,Nf]) or one per slice ([T,K,Nf]).
+// with_pre: dY ⊙ act'(pre) is formed as the kernel loads dY — for an fp32 dY by the narrow kernel (tmgcn_gemm_dw_act_f32),
+// for a dY stored in bf16 (dy_dt) by tmgcn_gemm_dw_act_bf16, which also widens it.
+static Tensor gemm_dw_any(const char* who, const Tensor& A, const Tensor& dY, at::ScalarType dy_dt, const Tensor& pre,
+                          bool with_pre, int64_t act, bool per_slice, int64_t algo) {
+  want(A, who, " A", at::kFloat);
+  want(dY, who, " dY", dy_dt);
+  TORCH_CHECK(A.dim() == 3 && dY.dim() == 3 && A.size(0) == dY.size(0) && A.size(1) == dY.size(1), who, ": A ", A.sizes(),
+              " and dY ", dY.sizes(), " do not match");
+  if (with_pre) {
+    want(pre, who, " pre-activation", at::kFloat);
+    TORCH_CHECK(pre.sizes() == dY.sizes(), who, ": pre ", pre.sizes(), " and dY ", dY.sizes(), " do not match");
+  }
   c10::DeviceGuard g(A.device());
   const int64_t T = A.size(0), N = A.size(1), K = A.size(2), Nf = dY.size(2), R = T * N;
   const int64_t rpb = per_slice ? N : 0;
+  const bool dy_bf16 = dy_dt == at::kBFloat16;
+  // no rows: the fp32 entry points zero-fill dW themselves, tmgcn_gemm_dw_act_bf16 leaves it as it is
+  if (dy_bf16 && R == 0) return per_slice ? at::zeros({T, K, Nf}, A.options()) : at::zeros({K, Nf}, A.options());
   const int64_t need = tmgcn_gemm_dw_workspace_bytes(R, (int32_t)K, (int32_t)Nf, rpb);
   // scratch from torch's caching allocator: stream-ordered, no synchronisation, graph-capturable
   Tensor ws = at::empty({need > 0 ? need : 1}, A.options().dtype(at::kByte));
   Tensor dW = per_slice ? at::empty({T, K, Nf}, A.options()) : at::empty({K, Nf}, A.options());
-  ok(tmgcn_gemm_dw_f32((const float*)ptr(A), (const float*)ptr(dY), (float*)ptr(dW), R, (int32_t)K, (int32_t)Nf,
-                       rpb, (int32_t)algo, ptr(ws), ws.numel(), stream_of(A)),
-     "tmgcn_gemm_dw_f32");
+  if (dy_bf16)
+    ok(tmgcn_gemm_dw_act_bf16((const float*)ptr(A), (const uint16_t*)ptr(dY), (const float*)ptr(pre), (int32_t)act,
+                              (float*)ptr(dW), R, (int32_t)K, (int32_t)Nf, rpb, ptr(ws), ws.numel(), stream_of(A)),
+       "tmgcn_gemm_dw_act_bf16");
+  else if (with_pre)
+    ok(tmgcn_gemm_dw_act_f32((const float*)ptr(A), (const float*)ptr(dY), (const float*)ptr(pre), (int32_t)act, (float*)ptr(dW),
+                             R, (int32_t)K, (int32_t)Nf, rpb, ptr(ws), ws.numel(), stream_of(A)),
+       "tmgcn_gemm_dw_act_f32");
+  else
+    ok(tmgcn_gemm_dw_f32((const float*)ptr(A), (const float*)ptr(dY), (float*)ptr(dW), R, (int32_t)K, (int32_t)Nf, rpb,
+                         (int32_t)algo, ptr(ws), ws.numel(), stream_of(A)),
+       "tmgcn_gemm_dw_f32");
   return dW;
 }
-
-// dW = Aᵀ·(dY ⊙ act'(pre)) in one launch (narrow layers; shared weight or one per slice)
+Tensor bgemm_dW(const Tensor& A, const Tensor& dY, bool per_slice, int64_t algo) {
+  return gemm_dw_any("gemm_dw", A, dY, at::kFloat, Tensor(), false, TMGCN_ACT_NONE, per_slice, algo);
+}
+// narrow layers (tmgcn_gemm_dw_act_supported)
 Tensor bgemm_dW_act(const Tensor& A, const Tensor& dY, const Tensor& pre, int64_t act, bool per_slice) {
-  want(A, "gemm_dw A");
-  want(dY, "gemm_dw dY");
-  want(pre, "gemm_dw pre-activation");
-  TORCH_CHECK(A.dim() == 3 && dY.dim() == 3 && A.size(0) == dY.size(0) && A.size(1) == dY.size(1) && pre.sizes() == dY.sizes(),
-              "gemm_dw_act: A ", A.sizes(), ", dY ", dY.sizes(), " and pre ", pre.sizes(), " do not match");
-  c10::DeviceGuard g(A.device());
-  const int64_t T = A.size(0), N = A.size(1), K = A.size(2), Nf = dY.size(2), R = T * N;
-  const int64_t rpb = per_slice ? N : 0;
-  const int64_t need = tmgcn_gemm_dw_workspace_bytes(R, (int32_t)K, (int32_t)Nf, rpb);
-  Tensor ws = at::empty({need > 0 ? need : 1}, A.options().dtype(at::kByte));
-  Tensor dW = per_slice ? at::empty({T, K, Nf}, A.options()) : at::empty({K, Nf}, A.options());
-  ok(tmgcn_gemm_dw_act_f32((const float*)ptr(A), (const float*)ptr(dY), (const float*)ptr(pre), (int32_t)act, (float*)ptr(dW), R,
-                           (int32_t)K, (int32_t)Nf, rpb, ptr(ws), ws.numel(), stream_of(A)),
-     "tmgcn_gemm_dw_act_f32");
-  return dW;
+  return gemm_dw_any("gemm_dw_act", A, dY, at::kFloat, pre, true, act, per_slice, TMGCN_DW_AUTO);
+}
+// pre: unused and may be absent for act = none
+Tensor gemm_dw_act_bf16(const Tensor& A, const Tensor& dY, const OptTensor& pre, int64_t act, bool per_slice) {
+  const bool with_pre = act != TMGCN_ACT_NONE;
+  return gemm_dw_any("gemm_dw_act_bf16", A, dY, at::kBFloat16, (with_pre && pre.has_value()) ? *pre : Tensor(), with_pre, act,
+                     per_slice, TMGCN_DW_AUTO);
 }
 
 Tensor edge_head_fwd(const Tensor& Z2, const Tensor& src, const Tensor& dst, const Tensor& U) {
@@ -695,53 +726,6 @@ struct RoundBf16Fn : public torch::autograd::Function<RoundBf16Fn> {
   }
 };
 
-// ---- the layer-1 GEMM of the bf16 activation path (csrc/gemm.hip: tmgcn_gemm_bf16y / tmgcn_gemm_dw_act_bf16) ------------
-bool gemm_bf16y_supported(int64_t K, int64_t Nf) {
-  return K >= 0 && Nf >= 0 && K <= INT32_MAX && Nf <= INT32_MAX && tmgcn_gemm_bf16y_supported((int32_t)K, (int32_t)Nf) != 0;
-}
-static bool aligned_to(const Tensor& t, uintptr_t n) { return !has(t) || reinterpret_cast<uintptr_t>(t.const_data_ptr()) % n == 0; }
-
-// act(A·W) stored in bf16 by the GEMM itself: A [T,N,K] fp32, W fp32 ([K,Nf] shared or [T,K,Nf] per slice); returns the bf16
-// Y and the fp32 pre-activation (want_pre and an activation), bit for bit bgemm's Y through round_bf16, and its pre
-std::tuple<Tensor, Tensor> gemm_bf16y(const Tensor& A, const Tensor& W, int64_t act, bool want_pre) {
-  want(A, "gemm_bf16y A");
-  want(W, "gemm_bf16y W");
-  TORCH_CHECK(A.dim() == 3, "gemm_bf16y: A must be [T,N,K]");
-  c10::DeviceGuard g(A.device());
-  const int64_t T = A.size(0), N = A.size(1), K = A.size(2);
-  const WShape s = w_shape(W, false, T, K, "gemm_bf16y");
-  Tensor Y = at::empty({T, N, s.wn}, A.options().dtype(at::kBFloat16));
-  Tensor pre = (want_pre && act != TMGCN_ACT_NONE) ? at::empty({T, N, s.wn}, A.options()) : Tensor();
-  ok(tmgcn_gemm_bf16y((const float*)ptr(A), (const float*)ptr(W), (uint16_t*)ptr(Y), (float*)ptr(pre), T * N, (int32_t)K,
-                      (int32_t)s.wn, s.per_slice ? N : 0, s.stride, (int32_t)act, stream_of(A)),
-     "tmgcn_gemm_bf16y");
-  return {Y, pre.defined() ? pre : none_like(A)};
-}
-
-// dW = Aᵀ·(widen(dY) ⊙ act'(pre)) in one launch from a bf16 dY (pre: fp32, unused and may be absent for act = none)
-Tensor gemm_dw_act_bf16(const Tensor& A, const Tensor& dY, const OptTensor& pre, int64_t act, bool per_slice) {
-  want(A, "gemm_dw_act_bf16 A");
-  want(dY, "gemm_dw_act_bf16 dY", at::kBFloat16);
-  TORCH_CHECK(A.dim() == 3 && dY.dim() == 3 && A.size(0) == dY.size(0) && A.size(1) == dY.size(1),
-              "gemm_dw_act_bf16: A ", A.sizes(), " and dY ", dY.sizes(), " do not match");
-  const Tensor pr = (act != TMGCN_ACT_NONE && pre.has_value()) ? *pre : Tensor();
-  if (act != TMGCN_ACT_NONE) {
-    want(pr, "gemm_dw_act_bf16 pre-activation");
-    TORCH_CHECK(pr.sizes() == dY.sizes(), "gemm_dw_act_bf16: pre ", pr.sizes(), " and dY ", dY.sizes(), " do not match");
-  }
-  c10::DeviceGuard g(A.device());
-  const int64_t T = A.size(0), N = A.size(1), K = A.size(2), Nf = dY.size(2), R = T * N;
-  const int64_t rpb = per_slice ? N : 0;
-  if (R == 0) return per_slice ? at::zeros({T, K, Nf}, A.options()) : at::zeros({K, Nf}, A.options());
-  const int64_t need = tmgcn_gemm_dw_workspace_bytes(R, (int32_t)K, (int32_t)Nf, rpb);
-  Tensor ws = at::empty({need > 0 ? need : 1}, A.options().dtype(at::kByte));
-  Tensor dW = per_slice ? at::empty({T, K, Nf}, A.options()) : at::empty({K, Nf}, A.options());
-  ok(tmgcn_gemm_dw_act_bf16((const float*)ptr(A), (const uint16_t*)ptr(dY), (const float*)ptr(pr), (int32_t)act, (float*)ptr(dW), R,
-                            (int32_t)K, (int32_t)Nf, rpb, ptr(ws), ws.numel(), stream_of(A)),
-     "tmgcn_gemm_dw_act_bf16");
-  return dW;
-}
-
 bool layer12_supported(int64_t K0, int64_t F, int64_t Nf) { return tmgcn_layer12_supported((int32_t)K0, (int32_t)F, (int32_t)Nf) != 0; }
 // ---- WD-GCN (wd_gcn_functions.py:66-98): relu(AX·W) + the LSTM recurrence, and its BPTT ----------------------------
 // `wide` selects the kernels of csrc/wdgcn_wide.hip (widths up to 64) through tmgcn_wdgcn_wide_*: the same operator,
@@ -1018,10 +1002,12 @@ int64_t abi_version() { return tmgcn_abi_version(); }
 // ---------------------------------------------------------------------------------------
 // differentiable operators (explicit adjoints: what autograd derives for the reference)
 // ---------------------------------------------------------------------------------------
+// X and / or Y may be stored in bf16 (`bf16`: the band kernel, plain row order): the backward is then ONE transposed launch
+// on the incoming gradient in the dtype it arrives in, writing dX in X's dtype — bf16 dY -> fp32 dX in the model's case.
 struct MTransformFn : public torch::autograd::Function<MTransformFn> {
   // Y[k] = Σ_j M[ro+k][co+j] X[j]   =>   dX[j] = Σ_k Mᵀ[co+j][ro+k] dY[k]
   static Tensor forward(AutogradContext* ctx, const Tensor& X, const Tensor& M, int64_t band_lo, int64_t band_hi,
-                        int64_t row_off, int64_t col_off, int64_t T_out, int64_t xg, int64_t yg) {
+                        int64_t row_off, int64_t col_off, int64_t T_out, int64_t xg, int64_t yg, bool bf16, bool out_bf16) {
     at::AutoDispatchBelowADInplaceOrView guard;
     ctx->save_for_backward({M});
     ctx->saved_data["lo"] = band_lo;
@@ -1031,44 +1017,27 @@ struct MTransformFn : public torch::autograd::Function<MTransformFn> {
     ctx->saved_data["T_in"] = X.size(0);
     ctx->saved_data["xg"] = xg;
     ctx->saved_data["yg"] = yg;
-    return mtransform(M, X, false, row_off, col_off, T_out, band_lo, band_hi, xg, yg);
-  }
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    const Tensor M = ctx->get_saved_variables()[0];
-    auto& d = ctx->saved_data;
-    Tensor dX = mtransform(M, grads[0].contiguous(), true, d["co"].toInt(), d["ro"].toInt(), d["T_in"].toInt(),
-                           d["hi"].toInt(), d["lo"].toInt(), d["yg"].toInt(), d["xg"].toInt());
-    return {dX, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
-
-// The same with X and / or Y stored in bf16 (band operators): the backward is ONE transposed launch on the incoming
-// gradient in the dtype it arrives in, writing dX in X's dtype — bf16 dY -> fp32 dX in the model's case.
-struct MTransformBf16Fn : public torch::autograd::Function<MTransformBf16Fn> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& X, const Tensor& M, int64_t band_lo, int64_t band_hi,
-                        int64_t row_off, int64_t col_off, int64_t T_out, bool out_bf16) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    ctx->save_for_backward({M});
-    ctx->saved_data["lo"] = band_lo;
-    ctx->saved_data["hi"] = band_hi;
-    ctx->saved_data["ro"] = row_off;
-    ctx->saved_data["co"] = col_off;
-    ctx->saved_data["T_in"] = X.size(0);
-    ctx->saved_data["x_bf16"] = X.scalar_type() == at::kBFloat16;
-    return mtransform_bf16(M, X, false, row_off, col_off, T_out, band_lo, band_hi, out_bf16);
+    if (X.scalar_type() == at::kBFloat16) ctx->saved_data["x_bf16"] = true;  // fp32 X: nothing more is kept than before
+    return bf16 ? mtransform_bf16(M, X, false, row_off, col_off, T_out, band_lo, band_hi, out_bf16)
+                : mtransform(M, X, false, row_off, col_off, T_out, band_lo, band_hi, xg, yg);
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     at::AutoDispatchBelowADInplaceOrView guard;
     const Tensor M = ctx->get_saved_variables()[0];
     auto& d = ctx->saved_data;
     const Tensor g = grads[0].contiguous();
-    const bool x_bf16 = d["x_bf16"].toBool();
-    Tensor dX = (x_bf16 || g.scalar_type() == at::kBFloat16)
-                    ? mtransform_bf16(M, g, true, d["co"].toInt(), d["ro"].toInt(), d["T_in"].toInt(), d["hi"].toInt(), d["lo"].toInt(),
-                                      x_bf16)
-                    : mtransform(M, g, true, d["co"].toInt(), d["ro"].toInt(), d["T_in"].toInt(), d["hi"].toInt(), d["lo"].toInt(), 0, 0);
-    return {dX, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    // the transposed launch: row and column offsets change places, and so do the two band widths and the two groupings
+    const int64_t t_ro = d["co"].toInt(), t_co = d["ro"].toInt(), t_lo = d["hi"].toInt(), t_hi = d["lo"].toInt();
+    const int64_t t_xg = d["yg"].toInt(), t_yg = d["xg"].toInt(), T_in = d["T_in"].toInt();
+    const bool x_bf16 = d.count("x_bf16") > 0;
+    // an fp32 X whose gradient arrives in fp32 is the fp32 entry's case (autograd hands a gradient over in Y's dtype)
+    const bool bf16 = x_bf16 || g.scalar_type() == at::kBFloat16;
+    TORCH_CHECK(!bf16 || (t_xg == 0 && t_yg == 0), "m_transform backward: grouped rows with a bf16-stored operand");
+    Tensor dX = bf16 ? mtransform_bf16(M, g, true, t_ro, t_co, T_in, t_lo, t_hi, x_bf16)
+                     : mtransform(M, g, true, t_ro, t_co, T_in, t_lo, t_hi, t_xg, t_yg);
+    variable_list out(11);
+    out[0] = dX;
+    return out;
   }
 };
 
@@ -1102,61 +1071,32 @@ struct SpmmFn : public torch::autograd::Function<SpmmFn> {
   }
 };
 
-struct FeatureGemmFn : public torch::autograd::Function<FeatureGemmFn> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& A, const Tensor& W, int64_t act) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    auto [Y, pre] = bgemm(A, W, false, act, act != TMGCN_ACT_NONE, TMGCN_GEMM_AUTO);
-    ctx->saved_data["act"] = act;
-    ctx->save_for_backward({A, W, pre});
-    return Y;
-  }
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    auto sv = ctx->get_saved_variables();
-    const Tensor &A = sv[0], &W = sv[1], &pre = sv[2];
-    const int64_t act = ctx->saved_data["act"].toInt();
-    Tensor dY = grads[0].contiguous();
-    Tensor dA, dW;
-    // layer 1 of the 2-layer models: the input (AtXt / AX) is a constant, so only dW is asked for — the activation
-    // gradient is folded into the dW kernel and dY ⊙ act'(pre) never exists as a tensor
-    const bool fold_act = act != TMGCN_ACT_NONE && !ctx->needs_input_grad(0) && ctx->needs_input_grad(1) && A.dim() == 3 &&
-                          tmgcn_gemm_dw_act_supported((int32_t)A.size(-1), (int32_t)dY.size(-1)) &&
-                          reinterpret_cast<uintptr_t>(A.const_data_ptr()) % 8 == 0 &&
-                          reinterpret_cast<uintptr_t>(dY.const_data_ptr()) % 8 == 0 &&
-                          reinterpret_cast<uintptr_t>(pre.const_data_ptr()) % 8 == 0;
-    if (fold_act) {
-      dW = bgemm_dW_act(A, dY, pre, act, W.dim() == 3);
-      if (dW.scalar_type() != W.scalar_type()) dW = dW.to(W.scalar_type());
-      return {dA, dW, Tensor()};
-    }
-    if (act != TMGCN_ACT_NONE) dY = act_bwd(pre, dY, act);
-    if (ctx->needs_input_grad(0)) dA = std::get<0>(bgemm(dY, W, true, TMGCN_ACT_NONE, false, TMGCN_GEMM_AUTO));
-    if (ctx->needs_input_grad(1)) {
-      dW = bgemm_dW(A, dY, W.dim() == 3, TMGCN_DW_AUTO);  // summed in fp32, rounded once for a bf16 parameter
-      if (dW.scalar_type() != W.scalar_type()) dW = dW.to(W.scalar_type());
-    }
-    return {dA, dW, Tensor()};
-  }
-};
+static bool aligned_to(const Tensor& t, uintptr_t n) { return !has(t) || reinterpret_cast<uintptr_t>(t.const_data_ptr()) % n == 0; }
+// What the bf16-Y kernels (tmgcn_gemm_bf16y, tmgcn_gemm_dw_act_bf16; the rule is csrc/gemm.hip's) ask of the operands they
+// are given: 16 / 8 / 16 bytes for A / the bf16 dY / pre, element alignment below K = 16.  An absent operand passes.
+static bool bf16y_aligned(const Tensor& A, const Tensor& dY, const Tensor& pre) {
+  const bool small = A.size(-1) < 16;
+  return aligned_to(A, small ? 4 : 16) && aligned_to(dY, small ? 2 : 8) && aligned_to(pre, small ? 4 : 16);
+}
 
-// act(A·W) with the result STORED in bf16 — layer 1 in front of the bf16 gather (EmbeddingGCN2(act_dtype=bfloat16), default
-// branch).  One launch each way where the kernels of tmgcn_gemm_bf16y cover the widths and the operands are aligned; else
-// the composition they replace (bgemm + cast forward; widen + act_bwd + bgemm / bgemm_dW backward), which gives the same bits.
-struct FeatureGemmBf16yFn : public torch::autograd::Function<FeatureGemmBf16yFn> {
-  static bool small_route(int64_t K) { return K < 16; }
-  static Tensor forward(AutogradContext* ctx, const Tensor& A, const Tensor& W, int64_t act) {
+// act(A·W).  y_bf16: the result is STORED in bf16 — layer 1 in front of the bf16 gather (EmbeddingGCN2(act_dtype=bfloat16),
+// default branch) — by one launch each way where the kernels of tmgcn_gemm_bf16y cover the widths and the operands are
+// aligned; else by the composition they replace (bgemm + cast forward; widen + act_bwd + bgemm / bgemm_dW backward), which
+// gives the same bits.
+struct FeatureGemmFn : public torch::autograd::Function<FeatureGemmFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& A, const Tensor& W, int64_t act, bool y_bf16) {
     at::AutoDispatchBelowADInplaceOrView guard;
-    const bool fused = A.defined() && A.dim() == 3 && W.defined() && W.scalar_type() == at::kFloat && A.numel() > 0 &&
-                       gemm_bf16y_supported(A.size(-1), W.size(-1)) && aligned_to(A, small_route(A.size(-1)) ? 4 : 16);
+    const bool fused = y_bf16 && A.defined() && A.dim() == 3 && W.defined() && W.scalar_type() == at::kFloat && A.numel() > 0 &&
+                       gemm_bf16y_supported(A.size(-1), W.size(-1)) && bf16y_aligned(A, Tensor(), Tensor());
     Tensor Y, pre;
     if (fused) {
       std::tie(Y, pre) = gemm_bf16y(A, W, act, act != TMGCN_ACT_NONE);
     } else {
-      Tensor Yf;
-      std::tie(Yf, pre) = bgemm(A, W, false, act, act != TMGCN_ACT_NONE, TMGCN_GEMM_AUTO);
-      Y = Yf.numel() ? cast_multi({Yf}, true)[0] : Yf.to(at::kBFloat16);
+      std::tie(Y, pre) = bgemm(A, W, false, act, act != TMGCN_ACT_NONE, TMGCN_GEMM_AUTO);
+      if (y_bf16) Y = Y.numel() ? cast_multi({Y}, true)[0] : Y.to(at::kBFloat16);
     }
     ctx->saved_data["act"] = act;
+    if (y_bf16) ctx->saved_data["y_bf16"] = true;  // fp32 Y: nothing more is kept than before
     ctx->save_for_backward({A, W, pre});
     return Y;
   }
@@ -1165,24 +1105,28 @@ struct FeatureGemmBf16yFn : public torch::autograd::Function<FeatureGemmBf16yFn>
     auto sv = ctx->get_saved_variables();
     const Tensor &A = sv[0], &W = sv[1], &pre = sv[2];
     const int64_t act = ctx->saved_data["act"].toInt();
+    const bool y_bf16 = ctx->saved_data.count("y_bf16") > 0;
     Tensor dY = grads[0].contiguous();
     Tensor dA, dW;
-    const bool small = small_route(A.size(-1));
-    // the gather's bf16 gradient as it arrives, act' folded into the dW operand load: no widened dY, no dY ⊙ act'(pre)
-    const bool fused = dY.scalar_type() == at::kBFloat16 && !ctx->needs_input_grad(0) && ctx->needs_input_grad(1) && A.dim() == 3 &&
-                       dY.numel() > 0 && gemm_bf16y_supported(A.size(-1), dY.size(-1)) && aligned_to(A, small ? 4 : 16) &&
-                       aligned_to(dY, small ? 2 : 8) && (act == TMGCN_ACT_NONE || aligned_to(pre, small ? 4 : 16));
-    if (fused) {
-      dW = gemm_dw_act_bf16(A, dY, pre, act, W.dim() == 3);
+    const bool dy_bf16 = dY.scalar_type() == at::kBFloat16;
+    // layer 1 of the 2-layer models: the input (AtXt / AX) is a constant, so only dW is asked for — the activation
+    // gradient is folded into the dW kernel and dY ⊙ act'(pre) never exists as a tensor
+    const bool only_dw = !ctx->needs_input_grad(0) && ctx->needs_input_grad(1) && A.dim() == 3;
+    if (only_dw && !y_bf16 && act != TMGCN_ACT_NONE && tmgcn_gemm_dw_act_supported((int32_t)A.size(-1), (int32_t)dY.size(-1)) &&
+        aligned_to(A, 8) && aligned_to(dY, 8) && aligned_to(pre, 8)) {
+      dW = bgemm_dW_act(A, dY, pre, act, W.dim() == 3);  // the narrow kernel's fold
+    } else if (only_dw && y_bf16 && dy_bf16 && dY.numel() > 0 && gemm_bf16y_supported(A.size(-1), dY.size(-1)) &&
+               bf16y_aligned(A, dY, pre)) {
+      dW = gemm_dw_act_bf16(A, dY, pre, act, W.dim() == 3);  // the gather's bf16 gradient as it arrives: no widened dY either
     } else {
-      if (dY.scalar_type() == at::kBFloat16) dY = dY.numel() ? cast_multi({dY}, false)[0] : dY.to(at::kFloat);
+      if (dy_bf16) dY = dY.numel() ? cast_multi({dY}, false)[0] : dY.to(at::kFloat);
       if (act != TMGCN_ACT_NONE) dY = act_bwd(pre, dY, act);
       if (ctx->needs_input_grad(0)) dA = std::get<0>(bgemm(dY, W, true, TMGCN_ACT_NONE, false, TMGCN_GEMM_AUTO));
       if (ctx->needs_input_grad(1)) dW = bgemm_dW(A, dY, W.dim() == 3, TMGCN_DW_AUTO);
     }
     // summed in fp32, rounded once for a bf16 parameter
     if (dW.defined() && dW.scalar_type() != W.scalar_type()) dW = dW.to(W.scalar_type());
-    return {dA, dW, Tensor()};
+    return {dA, dW, Tensor(), Tensor()};
   }
 };
 
@@ -1599,11 +1543,11 @@ struct WeightedCeFn : public torch::autograd::Function<WeightedCeFn> {
 
 Tensor m_transform_ad(const Tensor& X, const Tensor& M, int64_t band_lo, int64_t band_hi, int64_t row_off,
                       int64_t col_off, int64_t T_out, int64_t xg, int64_t yg) {
-  return MTransformFn::apply(X, M, band_lo, band_hi, row_off, col_off, T_out, xg, yg);
+  return MTransformFn::apply(X, M, band_lo, band_hi, row_off, col_off, T_out, xg, yg, false, false);
 }
 Tensor m_transform_bf16_ad(const Tensor& X, const Tensor& M, int64_t band_lo, int64_t band_hi, int64_t row_off, int64_t col_off,
                            int64_t T_out, bool out_bf16) {
-  return MTransformBf16Fn::apply(X, M, band_lo, band_hi, row_off, col_off, T_out, out_bf16);
+  return MTransformFn::apply(X, M, band_lo, band_hi, row_off, col_off, T_out, 0, 0, true, out_bf16);
 }
 Tensor spmm_ad(const Tensor& X, const Tensor& rowptr, const Tensor& col, const Tensor& val, const OptTensor& t_rowptr,
                const OptTensor& t_col, const OptTensor& t_val, int64_t N, double avg, const OptTensor& g_rows,
@@ -1611,8 +1555,8 @@ Tensor spmm_ad(const Tensor& X, const Tensor& rowptr, const Tensor& col, const T
   return SpmmFn::apply(X, rowptr, col, val, t_rowptr, t_col, t_val, N, avg, g_rows, g_chunks, t_g_rows, t_g_chunks,
                        at::GradMode::is_enabled() && X.requires_grad());
 }
-Tensor feature_gemm_ad(const Tensor& A, const Tensor& W, int64_t act) { return FeatureGemmFn::apply(A, W, act); }
-Tensor feature_gemm_bf16y_ad(const Tensor& A, const Tensor& W, int64_t act) { return FeatureGemmBf16yFn::apply(A, W, act); }
+Tensor feature_gemm_ad(const Tensor& A, const Tensor& W, int64_t act) { return FeatureGemmFn::apply(A, W, act, false); }
+Tensor feature_gemm_bf16y_ad(const Tensor& A, const Tensor& W, int64_t act) { return FeatureGemmFn::apply(A, W, act, true); }
 Tensor spmm_feature_gemm_ad(const Tensor& X, const Tensor& W, const Tensor& rowptr, const Tensor& col,
                             const Tensor& val, const OptTensor& t_rowptr, const OptTensor& t_col,
                             const OptTensor& t_val, int64_t N, double avg, int64_t act, int64_t grid_reserve,

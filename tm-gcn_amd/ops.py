@@ -421,32 +421,22 @@ kernels = HipKernels()
 # autograd
 # ---------------------------------------------------------------------------------------
 class _MTransform(torch.autograd.Function):
+    """out_dtype None: the fp32 transform.  Else X and / or Y stored in bf16 (plain row order): one launch each way, dX in
+    X's dtype.  The launcher is given out_dtype only where there is one (substituted kernels have the fp32 form alone)."""
+
     @staticmethod
-    def forward(ctx, X, op, row_off, col_off, T_out, x_group_rows, y_group_rows):
+    def forward(ctx, X, op, row_off, col_off, T_out, x_group_rows, y_group_rows, out_dtype):
         ctx.op, ctx.row_off, ctx.col_off, ctx.T_in = op, row_off, col_off, X.shape[0]
         ctx.xg, ctx.yg = x_group_rows, y_group_rows
-        return kernels.mtransform(op, X, False, row_off, col_off, T_out, x_group_rows, y_group_rows)
+        kw, ctx.back = ({}, {}) if out_dtype is None else (dict(out_dtype=out_dtype), dict(out_dtype=X.dtype))
+        return kernels.mtransform(op, X, False, row_off, col_off, T_out, x_group_rows, y_group_rows, **kw)
 
     @staticmethod
     def backward(ctx, dY):
         # Y[k] = Σ_j M[ro+k][co+j] X[j]   =>   dX[j] = Σ_k Mᵀ[co+j][ro+k] dY[k]
         dX = kernels.mtransform(ctx.op, dY.contiguous(), True, ctx.col_off, ctx.row_off, ctx.T_in,
-                                x_group_rows=ctx.yg, y_group_rows=ctx.xg)
-        return dX, None, None, None, None, None, None
-
-
-class _MTransformBf16(torch.autograd.Function):
-    """_MTransform with X and / or Y stored in bf16: one fused launch each way, dX in X's dtype."""
-
-    @staticmethod
-    def forward(ctx, X, op, row_off, col_off, T_out, out_dtype):
-        ctx.op, ctx.row_off, ctx.col_off, ctx.T_in, ctx.x_dtype = op, row_off, col_off, X.shape[0], X.dtype
-        return kernels.mtransform(op, X, False, row_off, col_off, T_out, out_dtype=out_dtype)
-
-    @staticmethod
-    def backward(ctx, dY):
-        dX = kernels.mtransform(ctx.op, dY.contiguous(), True, ctx.col_off, ctx.row_off, ctx.T_in, out_dtype=ctx.x_dtype)
-        return dX, None, None, None, None, None
+                                x_group_rows=ctx.yg, y_group_rows=ctx.xg, **ctx.back)
+        return dX, None, None, None, None, None, None, None
 
 
 class _Spmm(torch.autograd.Function):
@@ -461,45 +451,27 @@ class _Spmm(torch.autograd.Function):
         return kernels.spmm(ctx.A.transpose(), dY.contiguous(), tag="spmm_T"), None
 
 
+def _bf16y_aligned(A, dY=None, pre=None) -> bool:
+    """What the bf16-Y kernels (csrc/gemm.hip states the rule) ask of the operands they are given: 16 / 8 / 16 bytes for A /
+    the bf16 dY / pre, element alignment below K = 16."""
+    small = A.shape[-1] < 16
+    return (A.data_ptr() % (4 if small else 16) == 0 and (dY is None or dY.data_ptr() % (2 if small else 8) == 0)
+            and (pre is None or pre.data_ptr() % (4 if small else 16) == 0))
+
+
 class _FeatureGemm(torch.autograd.Function):
+    """act(A · W).  out_dtype=torch.bfloat16: Y stored in bf16 by the GEMM (the widths of gemm_bf16y_fused, an fp32 W): one
+    launch each way when the gradient arrives in bf16 and only W needs one; else the composition."""
+
     @staticmethod
-    def forward(ctx, A, W, act):
-        ctx.act = act if _lib.ACT_IDS[act] else None
+    def forward(ctx, A, W, act, out_dtype):
+        ctx.act, ctx.y_bf16 = (act if _lib.ACT_IDS[act] else None), _y_bf16(out_dtype)
+        kw = dict(out_dtype=out_dtype) if ctx.y_bf16 else {}      # substituted kernels have the fp32 form alone
         if ctx.act is not None:
-            Y, pre = kernels.gemm(A, W, act=act, want_pre=True)
+            Y, pre = kernels.gemm(A, W, act=act, want_pre=True, **kw)
             ctx.save_for_backward(A, W, pre)
         else:
-            Y = kernels.gemm(A, W)
-            ctx.save_for_backward(A, W)
-        return Y
-
-    @staticmethod
-    def backward(ctx, dY):
-        dY = dY.contiguous()
-        if ctx.act is not None:
-            A, W, pre = ctx.saved_tensors
-            dY = kernels.act_bwd(pre, dY, ctx.act)
-        else:
-            A, W = ctx.saved_tensors
-        dA = kernels.gemm(dY, W, trans_w=True) if ctx.needs_input_grad[0] else None
-        dW = kernels.gemm_dw(A, dY, per_slice=W.dim() == 3) if ctx.needs_input_grad[1] else None
-        if dW is not None and dW.dtype != W.dtype:
-            dW = dW.to(W.dtype)              # a bf16-stored parameter: summed in fp32, rounded once
-        return dA, dW, None
-
-
-class _FeatureGemmBf16y(torch.autograd.Function):
-    """_FeatureGemm with Y stored in bf16 by the GEMM (the widths of gemm_bf16y_fused, an fp32 W): one launch each way when
-    the gradient arrives in bf16 and only W needs one; else the composition."""
-
-    @staticmethod
-    def forward(ctx, A, W, act):
-        ctx.act = act if _lib.ACT_IDS[act] else None
-        if ctx.act is not None:
-            Y, pre = kernels.gemm(A, W, act=act, want_pre=True, out_dtype=torch.bfloat16)
-            ctx.save_for_backward(A, W, pre)
-        else:
-            Y = kernels.gemm(A, W, out_dtype=torch.bfloat16)
+            Y = kernels.gemm(A, W, **kw)
             ctx.save_for_backward(A, W)
         return Y
 
@@ -508,18 +480,17 @@ class _FeatureGemmBf16y(torch.autograd.Function):
         dY = dY.contiguous()
         A, W, *rest = ctx.saved_tensors
         pre = rest[0] if rest else None
-        small = A.shape[-1] < 16
-        if (dY.dtype == torch.bfloat16 and not ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
-                and A.data_ptr() % (4 if small else 16) == 0 and dY.data_ptr() % (2 if small else 8) == 0
-                and (pre is None or pre.data_ptr() % (4 if small else 16) == 0)):
-            return None, kernels.gemm_dw(A, dY, per_slice=W.dim() == 3, pre=pre, act=ctx.act), None
         if dY.dtype == torch.bfloat16:
+            if ctx.y_bf16 and not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _bf16y_aligned(A, dY, pre):
+                return None, kernels.gemm_dw(A, dY, per_slice=W.dim() == 3, pre=pre, act=ctx.act), None, None
             dY = kernels.ops.widen_params([dY])[0]
         if ctx.act is not None:
             dY = kernels.act_bwd(pre, dY, ctx.act)
         dA = kernels.gemm(dY, W, trans_w=True) if ctx.needs_input_grad[0] else None
         dW = kernels.gemm_dw(A, dY, per_slice=W.dim() == 3) if ctx.needs_input_grad[1] else None
-        return dA, dW, None
+        if dW is not None and dW.dtype != W.dtype:
+            dW = dW.to(W.dtype)              # a bf16-stored parameter: summed in fp32, rounded once
+        return dA, dW, None, None
 
 
 class _SpmmGemm(torch.autograd.Function):
@@ -628,7 +599,7 @@ def m_transform(X: torch.Tensor, op: MOperator, row_off=0, col_off=0, T_out=None
         if _registered():
             return kernels.ops.m_transform(X, op.M, op.band_lo, op.band_hi, row_off, col_off,
                                            -1 if T_out is None else T_out, x_group_rows, y_group_rows)
-        return _MTransform.apply(X, op, row_off, col_off, T_out, x_group_rows, y_group_rows)
+        return _MTransform.apply(X, op, row_off, col_off, T_out, x_group_rows, y_group_rows, None)
     if x_group_rows or y_group_rows:
         raise RuntimeError(f"x_group_rows={x_group_rows} / y_group_rows={y_group_rows} are not available with a bf16-stored "
                            "operand (the sharded layer exchanges fp32 activations)")
@@ -636,7 +607,7 @@ def m_transform(X: torch.Tensor, op: MOperator, row_off=0, col_off=0, T_out=None
         if _registered():
             return kernels.ops.m_transform_bf16(X, op.M, op.band_lo, op.band_hi, row_off, col_off,
                                                 -1 if T_out is None else T_out, y_bf16)
-        return _MTransformBf16.apply(X, op, row_off, col_off, T_out, torch.bfloat16 if y_bf16 else torch.float32)
+        return _MTransform.apply(X, op, row_off, col_off, T_out, 0, 0, torch.bfloat16 if y_bf16 else torch.float32)
     Y = m_transform(kernels.ops.widen_params([X])[0] if X.dtype == torch.bfloat16 else X, op, row_off, col_off, T_out)
     return round_bf16(Y) if y_bf16 else Y
 
@@ -679,12 +650,12 @@ def feature_gemm(A: torch.Tensor, W: torch.Tensor, act=None, out_dtype=None) -> 
     if not _y_bf16(out_dtype):
         if _registered():
             return kernels.ops.feature_gemm(A, W, _lib.ACT_IDS[act])
-        return _FeatureGemm.apply(A, W, act)
+        return _FeatureGemm.apply(A, W, act, None)
     if W.dtype == torch.float32 and gemm_bf16y_fused(A.shape[-1], W.shape[-1]):
         if _registered():
             return kernels.ops.feature_gemm_bf16y(A, W, _lib.ACT_IDS[act])
-        if A.data_ptr() % (4 if A.shape[-1] < 16 else 16) == 0:
-            return _FeatureGemmBf16y.apply(A, W, act)
+        if _bf16y_aligned(A):
+            return _FeatureGemm.apply(A, W, act, torch.bfloat16)
     return round_bf16(feature_gemm(A, W, act=act))
 
 
